@@ -20,8 +20,17 @@ second.
 Data: MuJoCo is not available, so the env is the synthetic HalfCheetah-shaped
 locomotion model (obs 17, act 6, horizon 1000); weights are random-init.
 
-Imitation quality (the reference benchmark's ``imit_stats.monitor_return_mean``, normalised
-``(R - R_random) / (R_expert - R_random)``: ``benchmarking/README.md:94-98``,
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline needs: it builds the
+trainer on random-policy demonstrations, warms up, times the K rounds, writes the outputs of the
+last timed round if ``--dump-outputs DIR`` is given, and prints the JSON line (the quality keys
+are null). ``--dump-outputs`` writes what a caller of the timed ``train()`` call is left with after
+its last round, as ``DIR/<name>.npy`` (float32 / float64, about 1 MB in all): the generator policy's
+and the reward net's ``state_dict`` entries, the last round's rollout buffers and the last round's
+discriminator statistics. With the same arguments the inputs (seeds, env resets, demonstrations)
+are identical from run to run.
+
+``--full`` adds the imitation quality (the reference benchmark's ``imit_stats.monitor_return_mean``,
+normalised ``(R - R_random) / (R_expert - R_random)``: ``benchmarking/README.md:94-98``,
 ``benchmarking/sacred_output_to_markdown_summary.py:79-140``), all OUTSIDE the timed region:
 
 1. before the trainer is built, a PPO expert of the same generator config is trained on the
@@ -33,7 +42,8 @@ Imitation quality (the reference benchmark's ``imit_stats.monitor_return_mean``,
 3. after the K timed rounds, training continues untimed to ``--quality-steps`` env steps
    per rank, then ``final_eval_return`` = mean of 50 deterministic ``device_evaluate``
    episodes; ``expert_return``, ``random_return`` and ``normalized_score`` are reported
-   alongside. ``--quality-steps 0`` (or the host engine) falls back to random-policy demos.
+   alongside. ``--quality-steps 0`` (or the host engine) falls back to random-policy demos and
+   evaluates the trained generator on the host env.
 """
 
 from __future__ import annotations
@@ -54,7 +64,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--engine", choices=["auto", "device", "host"], default=os.environ.get("IA_BENCH_ENGINE", "auto"))
     p.add_argument("--env", default="HalfCheetah-v4")
-    p.add_argument("--eval-episodes", type=int, default=50, help="final eval episodes (after timing); 0 = skip")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the imitation quality (expert, untimed imitation to --quality-steps, final "
+                        "evaluation); without it the run only sets up, warms up, times --steps rounds and reports")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed round computed as DIR/<name>.npy (float32 / float64)")
+    p.add_argument("--eval-episodes", type=int, default=50, help="--full: final eval episodes (after timing); 0 = skip")
     p.add_argument("--quality-steps", type=int, default=1_000_000,
                    help="imitation budget per rank (env steps, timed rounds included) before the final evaluation; "
                         "0 = imitate random-policy demos and skip the expert (device engine only)")
@@ -114,12 +129,49 @@ def fill_expert_cache(args):
     return "cached=True" in p.stdout
 
 
+def random_policy_demonstrations(env_id, seed, n_timesteps=16384):
+    """The recipe's random-policy stand-in demonstrations (``models.recipes.synthetic_demonstrations``:
+    same env seeds, envs and length) with the action space seeded too: its ``sample()`` otherwise draws
+    from OS entropy, and every run would imitate other transitions."""
+    from imitation_amd.data import rollout
+    from imitation_amd.util.util import make_vec_env
+
+    env = make_vec_env(env_id, rng=np.random.default_rng(12345), n_envs=16)
+    env.action_space.seed(12347 + seed)
+    trajs = rollout.generate_trajectories(None, env, rollout.make_min_timesteps(n_timesteps),
+                                          rng=np.random.default_rng(12346))
+    return rollout.flatten_trajectories(trajs)
+
+
+def dump_outputs(trainer, out_dir):
+    """What the timed ``train()`` call left its caller after its last round, one ``.npy`` per array:
+    the generator policy's and the reward net's ``state_dict`` entries (weights and running-norm
+    statistics), the device engine's rollout buffers of the last round and the last round's
+    discriminator statistics (one row per update). float64 stays, everything else becomes float32."""
+    import torch as th
+
+    arrays = {}
+    for prefix, module in (("policy", trainer.gen_algo.policy), ("reward_net", trainer.reward_train)):
+        for k, v in module.state_dict().items():
+            arrays[f"{prefix}.{k}"] = v
+    for k, v in getattr(trainer, "buf", {}).items():
+        arrays[f"rollout.{k}"] = v
+    if getattr(trainer, "_disc_stats_host", None) is not None:
+        arrays["disc_stats"] = trainer._disc_stats_host[:max(1, trainer.n_disc_updates_per_round)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if not isinstance(v, th.Tensor):
+            continue
+        a = v.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     child_cached = None
-    if args.quality_steps > 0 and args.eval_episodes > 0 and args.engine != "host" and args.expert_cache:
+    if args.full and args.quality_steps > 0 and args.eval_episodes > 0 and args.engine != "host" and args.expert_cache:
         child_cached = fill_expert_cache(args)
     import torch as th
 
@@ -143,7 +195,8 @@ def main():
     # imitation quality (reference benchmarking/README.md:94-98): untimed, before the trainer is
     # built -- a device-PPO expert trained on the env reward, its stochastic rollouts are the
     # demonstrations the timed GAIL trainer imitates (cached under --expert-cache)
-    quality = args.quality_steps > 0 and args.eval_episodes > 0 and device.type == "cuda" and args.engine != "host"
+    quality = (args.full and args.quality_steps > 0 and args.eval_episodes > 0 and device.type == "cuda"
+               and args.engine != "host")
     expert = None
     if quality:
         from imitation_amd.testing import imitation_quality as iq
@@ -156,7 +209,8 @@ def main():
     # the reference's tuned gail_seals_half_cheetah config (imitation_amd/models/recipes.py)
     built = models.build("gail_halfcheetah", device=device, n_envs=args.n_envs, engine=args.engine, seed=args.seed,
                          rank=rank, env_id=args.env, log_dir=os.path.join("/tmp", f"ia_bench_{os.getpid()}"),
-                         demonstrations=None if expert is None else expert["demos"])
+                         demonstrations=(random_policy_demonstrations(args.env, args.seed) if expert is None
+                                         else expert["demos"]))
     trainer, venv = built.trainer, built.venv
     engine = built.extras["engine"]
     n_steps = trainer.gen_algo.n_steps
@@ -183,6 +237,8 @@ def main():
     total_steps = steps_per_round * args.steps * world
     value = total_steps / dt
     # --- end of timed region ---
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)
     eval_return = None
     qual = dict(expert_return=None, random_return=None, normalized_score=None)
     if quality and engine == "device":  # untimed: imitate to the budget, then 50 deterministic episodes on the GPU
@@ -203,7 +259,7 @@ def main():
                     expert_in_child_process=child_cached is not None, expert_train_s=round(float(expert["expert_train_s"]), 3),
                     eval_episodes=args.eval_episodes)
         eval_return = round(eval_return, 3)
-    elif args.eval_episodes > 0:  # outside the timed region: mean return of the trained generator
+    elif args.full and args.eval_episodes > 0:  # outside the timed region: mean return of the trained generator
         from imitation_amd.rl.evaluation import evaluate_policy
 
         if hasattr(trainer, "sync_env_to_host"):

@@ -60,7 +60,7 @@ def _run(args, timeout=600):
 
 
 def test_bench_json_has_contract_and_quality_keys_on_cpu():
-    rec = _run(["--steps", "1", "--warmup", "0", "--eval-episodes", "2", "--engine", "host"])
+    rec = _run(["--full", "--steps", "1", "--warmup", "0", "--eval-episodes", "2", "--engine", "host"])
     for k in CONTRACT_KEYS + QUALITY_KEYS:
         assert k in rec, k
     assert rec["n_gpus"] == 1 and rec["steps"] == 1 and rec["warmup"] == 0
@@ -69,10 +69,54 @@ def test_bench_json_has_contract_and_quality_keys_on_cpu():
     assert rec["final_eval_return"] is not None
 
 
+def test_plain_run_is_lean_and_dumps_its_outputs_on_cpu(tmp_path):
+    """Without ``--full``: the contract keys, no quality work (null quality keys), and
+    ``--dump-outputs`` writes the same float arrays on a second run with the same arguments."""
+    import numpy as np
+
+    recs, dumps = [], []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        recs.append(_run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--engine", "host", "--dump-outputs", str(out)]))
+        dumps.append({f: np.load(out / f) for f in sorted(os.listdir(out))})
+    rec = recs[0]
+    for k in CONTRACT_KEYS + QUALITY_KEYS:
+        assert k in rec, k
+    assert rec["steps"] == 2 and rec["warmup"] == 0 and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(4096 * 1000.0 / rec["ms_per_step"], rel=1e-3)
+    assert all(rec[k] is None for k in QUALITY_KEYS) and "random-policy demos" in rec["data"]
+    a, b = dumps
+    assert a and sorted(a) == sorted(b) and all(f.endswith(".npy") for f in a)
+    assert any(f.startswith("policy.") for f in a) and any(f.startswith("reward_net.") for f in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), (f, a[f].dtype)
+        assert np.isfinite(a[f]).all(), f
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_device_round_on_gpu(tmp_path):
+    """One plain device-engine run: no quality phase, and the dump holds the last round's rollout
+    buffers ([T, N, ...] = [512, 8, ...]) and discriminator statistics besides the two nets."""
+    import numpy as np
+
+    rec = _run(["gpu", "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert rec["config"]["engine"] == "device" and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert all(rec[k] is None for k in QUALITY_KEYS) and "random-policy demos" in rec["data"]
+    dump = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert dump["rollout.obs_buf"].shape == (512, 8, 17) and dump["rollout.act_env"].shape == (512, 8, 6)
+    assert dump["disc_stats"].shape == (8, 8)
+    assert any(k.startswith("policy.") for k in dump) and any(k.startswith("reward_net.") for k in dump)
+    for k, v in dump.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+    assert np.abs(dump["rollout.obs_buf"]).max() > 0 and np.abs(dump["rollout.rewards"]).max() > 0
+
+
 @pytest.mark.gpu
 def test_bench_quality_phase_on_gpu(tmp_path):
     """Short budgets: the expert phase runs, then a second run reuses the cached demonstrations."""
-    args = ["gpu", "--steps", "2", "--warmup", "1", "--expert-steps", "300000", "--quality-steps", "200000",
+    args = ["gpu", "--full", "--steps", "2", "--warmup", "1", "--expert-steps", "300000", "--quality-steps", "200000",
             "--eval-episodes", "10", "--expert-cache", str(tmp_path)]
     a = _run(args)
     for k in QUALITY_KEYS:
