@@ -167,7 +167,9 @@ void reward_outnorm(py::dict d) {
   IA_HIP_CHECK2(ia::reward_outnorm_launch(a, ia_stream()));
 }
 
-void ppo_update(py::dict d) {
+// The shape and planning fields of PPOArgs (what ppo_rc_plan / ppo_lds_bytes read): the part of
+// the dict that engine_ppo_update, engine_ppo_plan, engine_ppo_path and engine_ppo_lds share.
+ia::PPOArgs ppo_shape_args(const py::dict& d) {
   ia::PPOArgs a{};
   a.D = ival(d, "D");
   a.A = ival(d, "A");
@@ -180,14 +182,31 @@ void ppo_update(py::dict d) {
   a.n_vf = (int)vid.size() - 1;
   for (size_t i = 0; i < pid.size(); ++i) a.pi_dims[i] = pid[i];
   for (size_t i = 0; i < vid.size(); ++i) a.vf_dims[i] = vid[i];
+  a.log_std_off = ival(d, "log_std_off", -1);
+  a.hidden_act = ival(d, "hidden_act", 0);  // selects the shape-specialised instance family
+  a.rows = ival(d, "rows");
+  a.batch = ival(d, "batch");
+  a.n_epochs = ival(d, "n_epochs");
+  a.rc_gmax = ival(d, "rc_gmax", 0);
+  a.rc_cw = ival(d, "rc_cw", 0);
+  a.rc_cus = ival(d, "rc_cus", 0);
+  return a;
+}
+
+// The register-chained plan of a configuration; false: engine_ppo_update (mode 0) runs ppo.hip.
+bool ppo_plan_rc(const py::dict& d, ia::PPORcPlan& plan) {
+  return ival(d, "allow_rc", 1) && ia::ppo_rc_plan(ppo_shape_args(d), plan);
+}
+
+void ppo_update(py::dict d) {
+  TORCH_CHECK(d.contains("hidden_act"), "engine arg missing: hidden_act");
+  ia::PPOArgs a = ppo_shape_args(d);
   auto pw = d["pi_w_off"].cast<std::vector<int>>();
   auto pb = d["pi_b_off"].cast<std::vector<int>>();
   auto vw = d["vf_w_off"].cast<std::vector<int>>();
   auto vb = d["vf_b_off"].cast<std::vector<int>>();
   for (int l = 0; l < a.n_pi; ++l) { a.pi_w_off[l] = pw[l]; a.pi_b_off[l] = pb[l]; }
   for (int l = 0; l < a.n_vf; ++l) { a.vf_w_off[l] = vw[l]; a.vf_b_off[l] = vb[l]; }
-  a.log_std_off = ival(d, "log_std_off", -1);
-  a.hidden_act = ival(d, "hidden_act");
   a.params = tptr<float>(d, "params");
   a.grads = tptr<float>(d, "grads");
   a.exp_avg = tptr<float>(d, "exp_avg");
@@ -207,9 +226,6 @@ void ppo_update(py::dict d) {
   a.adv = tptr<const float>(d, "adv");
   a.returns = tptr<const float>(d, "returns");
   a.perm = tptr<const int>(d, "perm");
-  a.rows = ival(d, "rows");
-  a.batch = ival(d, "batch");
-  a.n_epochs = ival(d, "n_epochs");
   a.clip_range = (float)fval(d, "clip_range");
   a.ent_coef = (float)fval(d, "ent_coef");
   a.vf_coef = (float)fval(d, "vf_coef");
@@ -226,65 +242,57 @@ void ppo_update(py::dict d) {
   a.mb_index = ival(d, "mb_index", 0);
   a.prof = tptr<unsigned long long>(d, "prof", true);
   if (a.prof) TORCH_CHECK(py::cast<torch::Tensor>(d["prof"]).numel() >= 20, "prof: 20 int64 cycle counters (ppo_rc_kernel.h)");
-  a.rc_gmax = ival(d, "rc_gmax", 0);
-  a.rc_cw = ival(d, "rc_cw", 0);
   a.err = reinterpret_cast<unsigned*>(tptr<int>(d, "err", true));
   a.spin_limit = (unsigned)ival(d, "spin_limit", 0);
   a.debug_stall = ival(d, "debug_stall", 0);
-  a.rc_cus = ival(d, "rc_cus", 0);
   TORCH_CHECK(a.D <= 64, "obs dim <= 64");
-  ia::PPORcGeo geo;
-  size_t rc_lds = 0;
-  if (a.mode == 0 && ival(d, "allow_rc", 1) && ia::ppo_rc_plan(a, geo, rc_lds)) {
-    auto ws = torch::empty({(int64_t)ia::ppo_rc_workspace_floats(a)},
+  ia::PPORcPlan plan;
+  if (a.mode == 0 && ival(d, "allow_rc", 1) && ia::ppo_rc_plan(a, plan)) {
+    auto ws = torch::empty({(int64_t)plan.workspace_floats},
                            torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA, c10::hip::current_device()));
-    IA_HIP_CHECK2(ia::ppo_rc_launch(a, ws.data_ptr<float>(), ia_stream()));
+    IA_HIP_CHECK2(ia::ppo_rc_launch(a, plan, ws.data_ptr<float>(), ia_stream()));
     return;
   }
   IA_HIP_CHECK2(ia::ppo_launch(a, ia_stream()));
 }
 
-// Which kernel engine_ppo_update(mode 0) runs for this configuration: "rc" or "lds".
-std::string ppo_path(py::dict d) {
-  ia::PPOArgs a{};
-  a.D = ival(d, "D");
-  a.A = ival(d, "A");
-  a.discrete = ival(d, "discrete");
-  auto pid = d["pi_dims"].cast<std::vector<int>>();
-  auto vid = d["vf_dims"].cast<std::vector<int>>();
-  a.n_pi = (int)pid.size() - 1;
-  a.n_vf = (int)vid.size() - 1;
-  for (size_t i = 0; i < pid.size(); ++i) a.pi_dims[i] = pid[i];
-  for (size_t i = 0; i < vid.size(); ++i) a.vf_dims[i] = vid[i];
-  a.batch = ival(d, "batch");
-  a.rows = ival(d, "rows");
-  a.log_std_off = ival(d, "log_std_off", -1);
-  a.rc_gmax = ival(d, "rc_gmax", 0);
-  a.rc_cw = ival(d, "rc_cw", 0);
-  a.rc_cus = ival(d, "rc_cus", 0);
-  a.hidden_act = ival(d, "hidden_act", 0);  // selects the shape-specialised instance family
-  ia::PPORcGeo geo;
-  size_t lds = 0;
-  if (ival(d, "allow_rc", 1) && ia::ppo_rc_plan(a, geo, lds))
-    return "rc:g" + std::to_string(geo.G) + "x" + std::to_string(geo.nch) + "x" + std::to_string(geo.cw) + ":kt" +
-           std::to_string(geo.kt) + (geo.ns ? ":ns" : "");
-  return "lds";
+std::string ppo_path_of(const ia::PPORcGeo& g) {
+  return "rc:g" + std::to_string(g.G) + "x" + std::to_string(g.nch) + "x" + std::to_string(g.cw) + ":kt" +
+         std::to_string(g.kt) + (g.ns ? ":ns" : "");
 }
 
-size_t ppo_lds(py::dict d) {
-  ia::PPOArgs a{};
-  a.D = ival(d, "D");
-  a.A = ival(d, "A");
-  a.discrete = ival(d, "discrete");
-  auto pid = d["pi_dims"].cast<std::vector<int>>();
-  auto vid = d["vf_dims"].cast<std::vector<int>>();
-  a.n_pi = (int)pid.size() - 1;
-  a.n_vf = (int)vid.size() - 1;
-  for (size_t i = 0; i < pid.size(); ++i) a.pi_dims[i] = pid[i];
-  for (size_t i = 0; i < vid.size(); ++i) a.vf_dims[i] = vid[i];
-  a.batch = ival(d, "batch");
-  return ia::ppo_lds_bytes(a);
+// Which kernel engine_ppo_update(mode 0) runs for this configuration: "rc:..." or "lds".
+std::string ppo_path(py::dict d) {
+  ia::PPORcPlan plan;
+  return ppo_plan_rc(d, plan) ? ppo_path_of(plan.g) : "lds";
 }
+
+// The whole host plan of the register-chained update ({"path": "lds"} when it does not apply):
+// the chosen instance (ppo_rc_instances.h) and the launch geometry.
+py::dict ppo_plan(py::dict d) {
+  ia::PPORcPlan plan;
+  py::dict o;
+  if (!ppo_plan_rc(d, plan)) {
+    o["path"] = "lds";
+    return o;
+  }
+  const ia::PPORcGeo& g = plan.g;
+  const ia::PPORcRow& r = *plan.row;
+  o["path"] = ppo_path_of(g);
+  o["instance"] = r.name;
+  const std::pair<const char*, int> ints[] = {
+      {"KT", r.KT}, {"KW", r.KW}, {"KB", r.KB}, {"S0T", r.S0T}, {"NLT", r.NLT}, {"ACTT", r.ACTT}, {"HWT", r.HWT},
+      {"CWT", r.CWT}, {"DT", r.DT}, {"NW", r.NW}, {"ns", g.ns}, {"nw", g.nw}, {"bf3", g.bf3}, {"G", g.G},
+      {"nch", g.nch}, {"cw", g.cw}, {"kt", g.kt}, {"n_items", g.n_items}, {"n_witems", g.n_witems},
+      {"xchg2", g.xchg2}, {"xcd", g.xcd}, {"grid", (int)plan.grid}, {"block", (int)plan.block}};
+  for (const auto& kv : ints) o[kv.first] = kv.second;
+  o["lds_bytes"] = plan.lds_bytes;
+  o["lds_launch"] = plan.lds_launch;
+  o["workspace_floats"] = plan.workspace_floats;
+  return o;
+}
+
+size_t ppo_lds(py::dict d) { return ia::ppo_lds_bytes(ppo_shape_args(d)); }
 
 }  // namespace
 
@@ -352,5 +360,6 @@ void register_engine(py::module& m) {
   m.def("engine_reward_outnorm", &reward_outnorm, "NormalizedRewardNet output normalisation over a rollout");
   m.def("engine_ppo_update", &ppo_update, "persistent PPO update / DP minibatch grads / apply");
   m.def("engine_ppo_path", &ppo_path, "kernel used by engine_ppo_update mode 0 (rc | lds)");
+  m.def("engine_ppo_plan", &ppo_plan, "host plan of the register-chained PPO update: instance + launch geometry");
   m.def("engine_ppo_lds", &ppo_lds, "LDS bytes the PPO kernel needs for a configuration");
 }

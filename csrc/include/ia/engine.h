@@ -182,7 +182,8 @@ struct PPOArgs {
   int rc_cus;           // CU count to plan against (0 = query the current device)
 };
 
-// CUs of the current device (cached per device; IMITATION_AMD_PPO_CUS overrides, e.g. tests).
+// CUs of the current device (cached per device; 256 without one). Plans use PPOArgs::rc_cus
+// instead when it is set (tests, partitioned devices).
 int device_cu_count();
 
 // Geometry + workspace of the register-chained PPO kernel (ppo_rc.hip), planned on the host.
@@ -227,6 +228,26 @@ struct PPORcGeo {
   // blocks b % xcd == 0 work (logical id b / xcd), so under the observed round-robin dealing of
   // blocks over the 8 XCDs every cooperating workgroup shares one XCD's L2
   int xcd;
+};
+
+// One compiled instance of ppo_rc_kernel: its template arguments (ppo_rc_kernel.h) and entry
+// point. The table is csrc/kernels/ppo_rc_instances.h.
+struct PPORcRow {
+  const char* name;
+  int ns;  // net-split build (one net per workgroup)
+  int KT, KW, KB, S0T, NLT, ACTT, HWT, CWT, DT, NW;
+  void (*kernel)(PPOArgs, PPORcGeo);
+};
+
+// Everything about one register-chained update that is decided on the host, without a device
+// pointer: ppo_rc_plan fills it once, ppo_rc_launch adds the workspace pointers and launches.
+struct PPORcPlan {
+  PPORcGeo g;           // geometry incl. xchg2 / xcd (workspace pointers unset)
+  const PPORcRow* row;  // the instance that runs it
+  size_t lds_bytes;     // LDS the geometry needs
+  size_t lds_launch;    // LDS the launch asks for (padded to keep cooperating workgroups one per CU)
+  unsigned grid, block;
+  size_t workspace_floats;
 };
 
 }  // namespace ia

@@ -395,9 +395,8 @@ hipError_t rollout_post_launch(const RolloutPostArgs& a, hipStream_t s);
 hipError_t reward_outnorm_launch(const OutNormArgs& a, hipStream_t s);
 
 // ---- ppo_rc.hip: register-chained single-rank PPO update (falls back to ppo.hip)
-bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes);
-size_t ppo_rc_workspace_floats(const PPOArgs& a);
-hipError_t ppo_rc_launch(const PPOArgs& a, float* workspace, hipStream_t s);
+bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan);  // host only; false: outside the fast path
+hipError_t ppo_rc_launch(const PPOArgs& a, const PPORcPlan& plan, float* workspace, hipStream_t s);
 
 // ---- ppo.hip: persistent PPO update
 size_t ppo_lds_bytes(const PPOArgs& a);

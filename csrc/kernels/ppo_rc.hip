@@ -1,6 +1,8 @@
-// Register-chained PPO update: host planning, the parallel prep kernel and the launch of the
-// shape-specialised kernel instance (kernel template: ppo_rc_kernel.h; instances compiled in
-// ppo_rc_inst*.hip, declared extern below).
+// Register-chained PPO update: the parallel prep kernel, host planning and the launch.
+// The kernel template is ppo_rc_kernel.h; its compiled instances are the rows of the table in
+// ppo_rc_instances.h (compiled in ppo_rc_inst_*.hip, declared extern below). ppo_rc_plan picks
+// the first row whose compile-time constants fit the shape (rc_select) and takes the slot caps,
+// waves and weight-image format of the plan from that row; ppo_rc_launch runs the row's kernel.
 #include <stdio.h>
 
 #include "ppo_rc_kernel.h"
@@ -9,7 +11,7 @@
 namespace ia {
 namespace rc {
 
-IA_RC_INSTANCES(IA_RC_EXTERN)
+IA_RC_TABLE(IA_RC_EXTERN)
 
 // ---------------------------------------------------------------- prep (parallel over minibatches)
 // One workgroup per minibatch k = epoch * n_mb + mb, one wave per chunk (looping when the
@@ -156,73 +158,33 @@ __global__ __launch_bounds__(64 * kPrepWaves) void ppo_rc_prep_kernel(PPOArgs a,
 
 using namespace rc;
 
-// Shape-specialised instances (0 = generic). Shared by the plan (which sizes chunks / waves
-// for the instance that will run) and the launch. Every instance the plan can reach compiles
-// without scratch (tools/kernel_resources.py, profiles/r4_kernel_resources.md).
-enum RcInst : int {
-  RC_GENERIC = 0,
-  RC_NS_CHEETAH32,    // HalfCheetah / Walker2d FeedForward32Policy (tanh), net split
-  RC_NS_CARTPOLE32,   // CartPole FeedForward32Policy, net split
-  RC_NS_HOPPER64R,    // Hopper MlpPolicy [64, 64] ReLU (AIRL config)
-  RC_NS_WALKER64R,    // Walker2d MlpPolicy [64, 64] ReLU (DRLHP config)
-  RC_NS_64_D16,       // any 3-layer [64, 64] net, obs dim <= 16 (SB3 MlpPolicy default: CartPole, Hopper, ...)
-  RC_NS_64_D32,       // any 3-layer [64, 64] net, obs dim <= 32 (HalfCheetah / Walker2d / Ant, ...)
-  RC_CHEETAH32_64,    // both nets per workgroup, 64-row chunks
-  RC_CHEETAH32_32,    // the same, 32-row chunks
-  RC_HOPPER64R_32,
-  RC_WALKER64R_32,
-  RC_CARTPOLE32_64,
-  RC_64_D16,          // both nets per workgroup, 32-row chunks: any 3-layer [64, 64] net, obs dim <= 16
-  RC_64_D32,          // the same, obs dim <= 32, ReLU + Gaussian head
-};
+// The instance table as host rows, in selection order. Every row compiles without scratch
+// (tools/kernel_resources.py, profiles/r4_kernel_resources.md).
+static const PPORcRow kRcRows[] = {IA_RC_TABLE(IA_RC_ROW)};
 
-static bool rc_inst_is_bf3(int inst) {
-  return inst == RC_NS_CHEETAH32 || inst == RC_NS_CARTPOLE32 || inst == RC_NS_HOPPER64R || inst == RC_NS_WALKER64R ||
-         inst == RC_NS_64_D16 || inst == RC_NS_64_D32 || inst == RC_CHEETAH32_64 || inst == RC_CARTPOLE32_64;
-}
+static bool rc_row_bf3(const PPORcRow& r) { return rc_is_bf3(r.KT, r.S0T, r.NLT, r.HWT, r.CWT, r.NW); }
 
-static int rc_instance_raw(const PPOArgs& a, int kt, int cw, bool ns);
-
-// IMITATION_AMD_PPO_BF3=0: exact-fp32 PPO products. The split-bf16 instances are not selected
-// (the plan then takes a generic fp32 register-chained build, or the LDS kernel where no
-// scratch-free generic build exists -- slower, bit-for-bit the fp32 formulation)
-static int rc_instance(const PPOArgs& a, int kt, int cw, bool ns) {
-  const int inst = rc_instance_raw(a, kt, cw, ns);
-  const char* ev = getenv("IMITATION_AMD_PPO_BF3");
-  if (ev && ev[0] == '0' && rc_inst_is_bf3(inst)) return RC_GENERIC;
-  return inst;
-}
-
-static int rc_instance_raw(const PPOArgs& a, int kt, int cw, bool ns) {
-  const int hw = a.pi_dims[1];
-  bool uniform = a.n_pi == 3 && a.n_vf == 3;
-  for (int l = 1; l < 3 && uniform; ++l) uniform = a.pi_dims[l] == hw && a.vf_dims[l] == hw;
+// The instance that runs a shape: the first row whose compile-time constants all agree with it
+// (a constant the row leaves to run time -- ppo_rc_kernel.h, "Shape specialisation" -- agrees
+// with anything), so a row is never chosen for a shape its constants do not fit. nullptr: no
+// scratch-free build runs this shape. bf3_ok false passes over the split-bf16 rows.
+static const PPORcRow* rc_select(const PPOArgs& a, int kt, int cw, bool ns, bool bf3_ok) {
   const int s0 = (a.D + 3) / 4;
-  const bool gauss = !a.discrete;
-  const bool act_ok = a.hidden_act == 1 || a.hidden_act == 2;
-  if (ns) {
-    if (uniform && hw == 32 && s0 == 5 && a.hidden_act == 2 && kt == 2 && gauss) return RC_NS_CHEETAH32;
-    if (uniform && hw == 32 && s0 == 1 && a.hidden_act == 2 && kt == 2 && !gauss) return RC_NS_CARTPOLE32;
-    if (uniform && hw == 64 && s0 == 3 && a.hidden_act == 1 && kt == 4 && gauss) return RC_NS_HOPPER64R;
-    if (uniform && hw == 64 && s0 == 5 && a.hidden_act == 1 && kt == 4 && gauss) return RC_NS_WALKER64R;
-    if (uniform && hw == 64 && kt == 4 && act_ok && a.D <= 16) return RC_NS_64_D16;
-    if (uniform && hw == 64 && kt == 4 && act_ok && a.D <= 32) return RC_NS_64_D32;
-    return RC_GENERIC;
+  for (const PPORcRow& r : kRcRows) {
+    bool ok = r.ns == (int)ns && r.KT == kt && (r.CWT <= 0 || r.CWT == cw);
+    ok = ok && (r.NLT <= 0 || (a.n_pi == r.NLT && a.n_vf == r.NLT));
+    if (r.HWT > 0) {
+      for (int l = 1; l < a.n_pi; ++l) ok = ok && a.pi_dims[l] == r.HWT;
+      for (int l = 1; l < a.n_vf; ++l) ok = ok && a.vf_dims[l] == r.HWT;
+    }
+    ok = ok && (r.S0T > 0 ? s0 == r.S0T : (r.S0T == 0 || s0 <= -r.S0T));
+    ok = ok && (r.ACTT < 0 || r.ACTT == a.hidden_act) && (r.DT < 0 || r.DT == (a.discrete ? 1 : 0));
+    if (ok && (bf3_ok || !rc_row_bf3(r))) return &r;
   }
-  if (uniform && hw == 32 && s0 == 5 && a.hidden_act == 2 && kt == 2 && cw == 64 && gauss) return RC_CHEETAH32_64;
-  if (uniform && hw == 32 && s0 == 5 && a.hidden_act == 2 && kt == 2 && cw == 32 && gauss) return RC_CHEETAH32_32;
-  if (uniform && hw == 64 && s0 == 3 && a.hidden_act == 1 && kt == 4 && cw == 32 && gauss) return RC_HOPPER64R_32;
-  if (uniform && hw == 64 && s0 == 5 && a.hidden_act == 1 && kt == 4 && cw == 32 && gauss) return RC_WALKER64R_32;
-  if (uniform && hw == 32 && s0 == 1 && a.hidden_act == 2 && kt == 2 && cw == 64 && !gauss) return RC_CARTPOLE32_64;
-  if (uniform && hw == 64 && kt == 4 && cw == 32 && act_ok && a.D <= 16) return RC_64_D16;
-  // (ReLU + Gaussian head only: the Tanh and categorical builds of this size need scratch)
-  if (uniform && hw == 64 && kt == 4 && cw == 32 && a.hidden_act == 1 && a.D <= 32 && gauss) return RC_64_D32;
-  return RC_GENERIC;
+  return nullptr;
 }
 
 int device_cu_count() {
-  const char* ev = getenv("IMITATION_AMD_PPO_CUS");
-  if (ev && atoi(ev) > 0) return atoi(ev);
   static int cached[64] = {0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -234,60 +196,72 @@ int device_cu_count() {
   return cached[dev];
 }
 
-// Host planning: LDS images + parameter items + workgroup split. Returns false if the
-// configuration is outside the fast path (falls back to ppo.hip).
-// IMITATION_AMD_PPO_PLAN_DEBUG=1: which check rejected a plan (stderr)
-static bool plan_reject(int site) {
-  const char* ev = getenv("IMITATION_AMD_PPO_PLAN_DEBUG");
-  if (ev && ev[0] == '1') fprintf(stderr, "ppo_rc_plan: rejected at check %d\n", site);
-  return false;
-}
-
-bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
-  g = PPORcGeo{};
-  if (a.batch % 16 != 0 || a.batch <= 0 || a.rows % a.batch != 0 || a.D > 64 || a.A > 16) return plan_reject(1);
-  if (a.n_pi < 1 || a.n_vf < 1 || a.n_pi > kL || a.n_vf > kL) return plan_reject(2);
+// Host planning: the instance, LDS images + parameter items + workgroup split, and the launch
+// shape. Returns false if the configuration is outside the fast path (falls back to ppo.hip).
+// Environment overrides, all read here, once per plan:
+//   IMITATION_AMD_PPO_PLAN_DEBUG=1  which check rejected a plan, LDS bytes (stderr)
+//   IMITATION_AMD_PPO_NETSPLIT=0    both nets per workgroup
+//   IMITATION_AMD_PPO_BF3=0         exact-fp32 PPO products: the split-bf16 instances are not
+//       selected (the plan then takes a generic fp32 register-chained build, or the LDS kernel
+//       where no scratch-free generic build exists -- slower, bit-for-bit the fp32 formulation)
+//   IMITATION_AMD_PPO_XCHG2=0/1     forces the one- / two-level partial exchange
+bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan) {
+  plan = PPORcPlan{};
+  PPORcGeo& g = plan.g;
+  const auto env = [](const char* name, char v) {
+    const char* ev = getenv(name);
+    return ev && ev[0] == v;
+  };
+  const bool debug = env("IMITATION_AMD_PPO_PLAN_DEBUG", '1');
+  const bool env_ns = !env("IMITATION_AMD_PPO_NETSPLIT", '0'), env_bf3 = !env("IMITATION_AMD_PPO_BF3", '0');
+  const char* env_xchg2 = getenv("IMITATION_AMD_PPO_XCHG2");
+  const auto reject = [&](int site) {
+    if (debug) fprintf(stderr, "ppo_rc_plan: rejected at check %d\n", site);
+    return false;
+  };
+  if (a.batch % 16 != 0 || a.batch <= 0 || a.rows % a.batch != 0 || a.D > 64 || a.A > 16) return reject(1);
+  if (a.n_pi < 1 || a.n_vf < 1 || a.n_pi > kL || a.n_vf > kL) return reject(2);
   const int* dims[2] = {a.pi_dims, a.vf_dims};
   const int nls[2] = {a.n_pi, a.n_vf};
   int wmax = 0;
   for (int q = 0; q < 2; ++q)
     for (int l = 0; l + 1 < nls[q]; ++l) wmax = dims[q][l + 1] > wmax ? dims[q][l + 1] : wmax;
-  if (wmax > 64) return plan_reject(3);
+  if (wmax > 64) return reject(3);
   g.kt = wmax <= 32 ? 2 : 4;
   const int KT = g.kt;
-  g.nw = waves_for(KT);
-  const char* nsev = getenv("IMITATION_AMD_PPO_NETSPLIT");
   // net split: each workgroup runs ONE net (actor or critic) over 64-row chunks -- its 4
   // row-tile waves at one wave per SIMD, with half of the dW / Adam items a both-nets
   // workgroup owns -- and the two nets meet once per minibatch for clip_grad_norm_
-  const bool ns = !(nsev && nsev[0] == '0') && (a.rc_cw == 0 || a.rc_cw == 64) && a.batch % 64 == 0;
-  // workgroup split: chunks of cw rows (64 for narrow nets, 32 for 64-wide ones: LDS, and
-  // the 4-wave workgroup has 2 row-tile waves per net)
+  const bool ns = env_ns && (a.rc_cw == 0 || a.rc_cw == 64) && a.batch % 64 == 0;
+  // workgroup split: chunks of cw rows (64 for narrow nets and the net split, 32 for 64-wide
+  // nets with both nets per workgroup: LDS, and the 4-wave workgroup has 2 row-tile waves per net)
   int cw = KT == 2 || ns ? 64 : 32;
   if (a.rc_cw == 16 || a.rc_cw == 32 || (a.rc_cw == 64 && KT == 2)) cw = a.rc_cw;
   if (a.batch < cw) cw = a.batch;
-  if (a.batch % cw != 0) {
-    cw = 16;
-  }
-  bool narrow4 = false;  // generic both-nets build at one wave per SIMD (4 waves, <= 32-row chunks)
-  if (!(ns && cw == 64) && rc_instance(a, KT, cw, false) == RC_GENERIC) {
-    // the 8-wave generic build has 256 registers per wave and spills: run the 4-wave build
-    // (2 row-tile waves per net, 512 registers each) for <= 32-wide nets; 64-wide nets outside
-    // the [64, 64] family builds cannot hold their owned items without scratch -> the LDS kernel
-    if (KT == 4) return plan_reject(4);
-    narrow4 = true;
-    if (cw > 32) cw = 32;
+  if (a.batch % cw != 0) cw = 16;
+  // the instance. No row: the generic 8-wave both-nets build (256 registers per wave) and the
+  // generic 64-wide builds (owned items + vectors at run-time shapes) need scratch and are not
+  // compiled, so 64-wide nets outside the [64, 64] families take the LDS kernel
+  const PPORcRow* row = rc_select(a, KT, cw, ns, env_bf3);
+  if (row == nullptr) return reject(4);
+  if (row->CWT <= 0) {  // run-time chunk width: at most the rows the net's row-tile waves cover
+    const int cover = 16 * (ns ? row->NW : row->NW / 2);
+    if (cw > cover) cw = cover;
     if (a.batch % cw != 0) cw = 16;
   }
+  plan.row = row;
+  g.nw = row->NW;
+  g.ns = ns ? 1 : 0;
+  g.bf3 = rc_row_bf3(*row) ? 1 : 0;
   const int chunks = a.batch / cw;
+  const int cus = a.rc_cus > 0 ? a.rc_cus : device_cu_count();
+  const int per = ns ? 2 : 1;  // net split: two workgroups per row group
   int gmax = a.rc_gmax > 0 ? (a.rc_gmax < kMaxRcGroups ? a.rc_gmax : kMaxRcGroups) : kMaxRcGroups;
   {  // co-residency: every spinning workgroup must hold a CU of its own (> 80 KiB of LDS: one
      // per CU) while the rest of the chip stays free for concurrent streams (the discriminator
      // runs beside the update), so the working blocks are capped at half the device's CUs
-    const int cus = a.rc_cus > 0 ? a.rc_cus : device_cu_count();
-    const int per = (ns && cw == 64) ? 2 : 1;  // net split: two workgroups per row group
     const int cap = (cus / 2) / per;
-    if (cap < 1) return plan_reject(5);
+    if (cap < 1) return reject(5);
     if (gmax > cap) gmax = cap;
   }
   int G = 1;
@@ -299,15 +273,6 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
   g.cw = cw;
   g.G = G;
   g.nch = chunks / G;
-  g.ns = ns && cw == 64 ? 1 : 0;
-  if (g.ns || narrow4) g.nw = 4;
-  // the generic 64-wide net-split build needs scratch (8 weight slots + 2 vectors at runtime
-  // shapes): nets outside the specialised [64, 64] families take the LDS kernel
-  if (g.ns && KT == 4 && rc_instance(a, KT, cw, true) == RC_GENERIC) return plan_reject(6);
-  {  // the 32-wide specialised net-split builds run the split-bf16 forward / dX (kernel: BF3)
-    const int inst = rc_instance(a, KT, cw, g.ns != 0);
-    g.bf3 = rc_inst_is_bf3(inst) ? 1 : 0;
-  }
   int off = 0;
   auto take = [&](int n) {
     const int o = off;
@@ -323,9 +288,9 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
     for (int l = 0; l < nls[q]; ++l) {
       const int din = dims[q][l], dout = dims[q][l + 1];
       const bool last = l == nls[q] - 1;
-      if (!last && dout > 16 * KT) return plan_reject(7);
-      if (last && dout > 16) return plan_reject(8);
-      if (l > 0 && din > 16 * KT) return plan_reject(9);
+      if (!last && dout > 16 * KT) return reject(6);
+      if (last && dout > 16) return reject(7);
+      if (l > 0 && din > 16 * KT) return reject(8);
       g.din[q][l] = din;
       g.dout[q][l] = dout;
       const int ip = l == 0 ? ((din + 3) & ~3) : ((din + 15) & ~15);
@@ -380,9 +345,9 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
   g.red_off = take(8 + 8 * 5 + 4);  // wave |g|^2, wave stats, [48] both nets' |g|^2
   g.trash_off = take(64);
   g.lds_floats = off;
-  lds_bytes = (size_t)off * 4;
-  if (getenv("IMITATION_AMD_PPO_PLAN_DEBUG")) fprintf(stderr, "ppo_rc_plan: %zu B of LDS\n", lds_bytes);
-  if (lds_bytes > 160 * 1024) return plan_reject(10);
+  plan.lds_bytes = (size_t)off * 4;
+  if (debug) fprintf(stderr, "ppo_rc_plan: %s, %zu B of LDS\n", row->name, plan.lds_bytes);
+  if (plan.lds_bytes > 160 * 1024) return reject(9);
   // items: dW tiles first (ids [0, n_witems): a wave's weight items are its first slots),
   // actor's then critic's; then bias vectors: actor's, log_std (an actor item), critic's
   int n = 0;
@@ -392,7 +357,7 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
       const int to = (g.dout[q][l] + 15) / 16, ti = (g.din[q][l] + 15) / 16;
       for (int ta = 0; ta < to; ++ta)
         for (int tb = 0; tb < ti; ++tb) {
-          if (n >= kMaxRcItems) return plan_reject(11);
+          if (n >= kMaxRcItems) return reject(10);
           g.items[n++] = q | (l << 1) | (0 << 3) | (ta << 5) | (tb << 9);
         }
     }
@@ -402,71 +367,32 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcGeo& g, size_t& lds_bytes) {
   for (int q = 0; q < 2; ++q) {
     g.bbase[q] = n;
     for (int l = 0; l < nls[q]; ++l) {
-      if (n >= kMaxRcItems) return plan_reject(12);
+      if (n >= kMaxRcItems) return reject(11);
       g.items[n++] = q | (l << 1) | (1 << 3);
     }
     if (q == 0 && !a.discrete && a.log_std_off >= 0) {
-      if (n >= kMaxRcItems) return plan_reject(13);
+      if (n >= kMaxRcItems) return reject(12);
       g.items[n++] = 2 << 3;
     }
     g.nbit[q] = n - g.bbase[q];
   }
   g.n_items = n;
+  // a wave owns at most the KW weight tiles / KB vectors its instance was compiled with
   int wmx = g.n_witems, bmx = n - g.n_witems;
   if (g.ns) {
     wmx = g.nwit[0] > g.nwit[1] ? g.nwit[0] : g.nwit[1];
     bmx = g.nbit[0] > g.nbit[1] ? g.nbit[0] : g.nbit[1];
   }
-  int wcap = g.ns ? wslots_ns(KT) : wslots_for(KT), bcap = g.ns ? bslots_ns() : bslots_for(KT);
-  if (narrow4) {
-    wcap = kNarrow4W;
-    bcap = kNarrow4B;
-  }
-  {  // the specialised instances size their slots to the shape they were built for
-    const int inst = rc_instance(a, KT, cw, g.ns != 0);
-    if (inst == RC_NS_64_D16) { wcap = 6; bcap = 1; }
-    if (inst == RC_NS_64_D32) { wcap = 7; bcap = 1; }
-    if (inst == RC_64_D16) { wcap = 12; bcap = 2; }
-    if (inst == RC_64_D32) { wcap = 14; bcap = 2; }
-  }
-  if ((wmx + g.nw - 1) / g.nw > wcap || (bmx + g.nw - 1) / g.nw > bcap) return plan_reject(14);
+  if ((wmx + g.nw - 1) / g.nw > row->KW || (bmx + g.nw - 1) / g.nw > row->KB) return reject(13);
   g.dp = (a.D + 3) & ~3;
-  return true;
-}
-
-size_t ppo_rc_workspace_floats(const PPOArgs& a) {
-  PPORcGeo g;
-  size_t lds = 0;
-  if (!ppo_rc_plan(a, g, lds)) return 0;
-  const size_t K = (size_t)a.n_epochs * (a.rows / a.batch);
-  const size_t slots = K * g.G * g.nch;
-  return slots * 64 * (g.dp + 16 + 4) + K * 128 + 2 * (size_t)(g.G + 1) * g.n_items * 256 + 64;
-}
-
-hipError_t ppo_rc_launch(const PPOArgs& a, float* workspace, hipStream_t s) {
-  PPORcGeo g;
-  size_t lds = 0;
-  if (!ppo_rc_plan(a, g, lds)) return hipErrorInvalidValue;
-  const size_t K = (size_t)a.n_epochs * (a.rows / a.batch);
-  const size_t slots = K * g.G * g.nch;
-  g.xraw = workspace;
-  g.acts = g.xraw + slots * 64 * g.dp;
-  g.rowd = g.acts + slots * 64 * 16;
-  g.mom = g.rowd + slots * 64 * 4;
-  g.slab = g.mom + K * 128;
-  g.red = g.slab + 2 * (size_t)g.G * g.n_items * 256;
-  g.sync = reinterpret_cast<unsigned*>(g.red + 2 * (size_t)g.n_items * 256);
-  {  // two-level exchange from 4 (64-wide nets) / 16 (<= 32-wide) cooperating workgroups
-     // (IMITATION_AMD_PPO_XCHG2=0/1 forces it; measured: profiles/r3_ppo64_scale.md)
-    const char* ev = getenv("IMITATION_AMD_PPO_XCHG2");
-    g.xchg2 = ev ? (ev[0] == '1' && g.G > 1) : (g.G >= (g.kt == 4 ? 4 : 16));
-  }
-  if (K == 0) return hipSuccess;
+  // two-level exchange from 4 (64-wide nets) / 16 (<= 32-wide) cooperating workgroups
+  // (measured: profiles/r3_ppo64_scale.md)
+  g.xchg2 = env_xchg2 ? (env_xchg2[0] == '1' && G > 1) : (G >= (KT == 4 ? 4 : 16));
   // > 80 KiB of LDS keeps the cooperating workgroups one per CU (the measured condition of
   // the sc1 hand-off); all G <= kMaxRcGroups (64) of them are co-resident (256 CUs)
   // (net split: the two workgroups must not share a CU's matrix cores either)
-  size_t lds_launch = (g.G > 1 || g.ns) && lds < 96 * 1024 ? 96 * 1024 : lds;
-  const int nblk = g.ns ? 2 * g.G : g.G;
+  plan.lds_launch = (G > 1 || ns) && plan.lds_bytes < 96 * 1024 ? 96 * 1024 : plan.lds_bytes;
+  const int nblk = per * G;
   {  // cooperating workgroups on as few XCDs as possible (the "xcd" geometry field is the block
      // stride). GAIL emulated W = 2 / 4 / 8: 3.14 / 3.28 / 3.64 -> 2.99 / 2.96 / 3.36 ms per update,
      // headline round 3.63 -> 3.55 ms (profiles/r3_ppo_xcd.md)
@@ -478,82 +404,44 @@ hipError_t ppo_rc_launch(const PPOArgs& a, float* workspace, hipStream_t s) {
     g.xcd = 1;
     if (nblk > 1) g.xcd = nblk <= 16 ? 8 : nblk <= 32 ? 4 : nblk <= 64 ? 2 : 1;
     // never a wider stride than the device has XCDs (32 CUs each; a partitioned device has fewer)
-    const int cus = a.rc_cus > 0 ? a.rc_cus : device_cu_count();
     const int xcds = cus / 32 > 1 ? cus / 32 : 1;
     while (g.xcd > xcds) g.xcd >>= 1;
   }
-  const dim3 grid(nblk * g.xcd), block(64 * g.nw);
-  int wmx = g.n_witems, bmx = g.n_items - g.n_witems;
-  if (g.ns) {
-    wmx = g.nwit[0] > g.nwit[1] ? g.nwit[0] : g.nwit[1];
-    bmx = g.nbit[0] > g.nbit[1] ? g.nbit[0] : g.nbit[1];
-  }
-  const int nwslot = (wmx + g.nw - 1) / g.nw, nbslot = (bmx + g.nw - 1) / g.nw;
-  typedef void (*RcKernel)(PPOArgs, PPORcGeo);
-  RcKernel kern = nullptr;
-#define IA_RC(KT, KW, KB, S0, NL, ACT, HW, CW, DT) kern = ppo_rc_kernel<KT, KW, KB, S0, NL, ACT, HW, CW, DT, waves_for(KT)>
-#define IA_RC_NS(KT, KW, KB, S0, NL, ACT, HW, DT) kern = ppo_rc_kernel<KT, KW, KB, S0, NL, ACT, HW, 64, DT, 4>
-  const auto fits = [&](int kw, int kb) { return nwslot <= kw && nbslot <= kb; };
-  const bool cat = a.discrete != 0;
-  const int hact = a.hidden_act;
-  switch (rc_instance(a, g.kt, g.cw, g.ns != 0)) {
-    case RC_NS_CHEETAH32: if (fits(3, 1)) IA_RC_NS(2, 3, 1, 5, 3, 2, 32, 0); break;
-    case RC_NS_CARTPOLE32: if (fits(2, 1)) IA_RC_NS(2, 2, 1, 1, 3, 2, 32, 1); break;
-    case RC_NS_HOPPER64R: if (fits(6, 1)) IA_RC_NS(4, 6, 1, 3, 3, 1, 64, 0); break;
-    case RC_NS_WALKER64R: if (fits(7, 1)) IA_RC_NS(4, 7, 1, 5, 3, 1, 64, 0); break;
-    case RC_NS_64_D16:
-      if (hact == 1 && !cat) IA_RC_NS(4, 6, 1, -4, 3, 1, 64, 0);
-      else if (hact == 1) IA_RC_NS(4, 6, 1, -4, 3, 1, 64, 1);
-      else if (!cat) IA_RC_NS(4, 6, 1, -4, 3, 2, 64, 0);
-      else IA_RC_NS(4, 6, 1, -4, 3, 2, 64, 1);
-      break;
-    case RC_NS_64_D32:
-      if (hact == 1 && !cat) IA_RC_NS(4, 7, 1, -8, 3, 1, 64, 0);
-      else if (hact == 1) IA_RC_NS(4, 7, 1, -8, 3, 1, 64, 1);
-      else if (!cat) IA_RC_NS(4, 7, 1, -8, 3, 2, 64, 0);
-      else IA_RC_NS(4, 7, 1, -8, 3, 2, 64, 1);
-      break;
-    case RC_CHEETAH32_64: if (fits(3, 1)) IA_RC(2, 3, 1, 5, 3, 2, 32, 64, 0); break;
-    case RC_CHEETAH32_32: if (fits(3, 1)) IA_RC(2, 3, 1, 5, 3, 2, 32, 32, 0); break;
-    case RC_HOPPER64R_32: if (fits(12, 2)) IA_RC(4, 12, 2, 3, 3, 1, 64, 32, 0); break;
-    case RC_WALKER64R_32: if (fits(14, 2)) IA_RC(4, 14, 2, 5, 3, 1, 64, 32, 0); break;
-    case RC_CARTPOLE32_64: if (fits(2, 1)) IA_RC(2, 2, 1, 1, 3, 2, 32, 64, 1); break;
-    case RC_64_D16:
-      if (hact == 1 && !cat) IA_RC(4, 12, 2, -4, 3, 1, 64, 32, 0);
-      else if (hact == 1) IA_RC(4, 12, 2, -4, 3, 1, 64, 32, 1);
-      else if (!cat) IA_RC(4, 12, 2, -4, 3, 2, 64, 32, 0);
-      else IA_RC(4, 12, 2, -4, 3, 2, 64, 32, 1);
-      break;
-    case RC_64_D32:
-      IA_RC(4, 14, 2, -8, 3, 1, 64, 32, 0);
-      break;
-    default: break;
-  }
-  if (kern == nullptr) {
-    if (g.ns && g.kt == 2)
-      IA_RC_NS(2, wslots_ns(2), bslots_ns(), 0, 0, -1, 0, -1);
-    else if (g.kt == 2 && g.nw == 4)
-      kern = ppo_rc_kernel<2, kNarrow4W, kNarrow4B, 0, 0, -1, 0, 0, -1, 4>;
-    else
-      return hipErrorInvalidValue;  // the plan never selects a spilling generic build
-  }
-#undef IA_RC
-#undef IA_RC_NS
+  plan.grid = nblk * g.xcd;
+  plan.block = 64 * g.nw;
+  const size_t K = (size_t)a.n_epochs * (a.rows / a.batch);
+  plan.workspace_floats = K * G * g.nch * 64 * (g.dp + 16 + 4) + K * 128 + 2 * (size_t)(G + 1) * g.n_items * 256 + 64;
+  return true;
+}
+
+hipError_t ppo_rc_launch(const PPOArgs& a, const PPORcPlan& plan, float* workspace, hipStream_t s) {
+  PPORcGeo g = plan.g;
+  const size_t K = (size_t)a.n_epochs * (a.rows / a.batch);
+  const size_t slots = K * g.G * g.nch;
+  g.xraw = workspace;
+  g.acts = g.xraw + slots * 64 * g.dp;
+  g.rowd = g.acts + slots * 64 * 16;
+  g.mom = g.rowd + slots * 64 * 4;
+  g.slab = g.mom + K * 128;
+  g.red = g.slab + 2 * (size_t)g.G * g.n_items * 256;
+  g.sync = reinterpret_cast<unsigned*>(g.red + 2 * (size_t)g.n_items * 256);
+  if (K == 0) return hipSuccess;
+  const int nblk = g.ns ? 2 * g.G : g.G;
   if (nblk > 1) {
     // every working block must be resident at once: check the instance's occupancy at this
     // LDS size against the device (the plan capped the working blocks at half the CUs)
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), (int)block.x,
-                                                     lds_launch) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(plan.row->kernel),
+                                                     (int)plan.block, plan.lds_launch) != hipSuccess)
       per_cu = 1;
-    if (per_cu > 1 && lds_launch > 80 * 1024) per_cu = 1;  // LDS holds one block per CU (the API can read high)
+    if (per_cu > 1 && plan.lds_launch > 80 * 1024) per_cu = 1;  // LDS holds one block per CU (the API can read high)
     const int cus = a.rc_cus > 0 ? a.rc_cus : device_cu_count();
     if (per_cu < 1 || (long long)per_cu * cus < (long long)nblk) return hipErrorCooperativeLaunchTooLarge;
   }
   const int CH = g.G * g.nch;
   const int prep_waves = CH < kPrepWaves ? CH : kPrepWaves;
   hipLaunchKernelGGL(ppo_rc_prep_kernel, dim3((unsigned)K), dim3(64 * prep_waves), 0, s, a, g);
-  hipLaunchKernelGGL(kern, grid, block, lds_launch, s, a, g);
+  hipLaunchKernelGGL(plan.row->kernel, dim3(plan.grid), dim3(plan.block), plan.lds_launch, s, a, g);
   return hipGetLastError();
 }
 

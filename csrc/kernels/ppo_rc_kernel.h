@@ -404,6 +404,14 @@ __device__ __forceinline__ void bf3_store_tile(lf* L, int kind, int wf, int wfl,
   }
 }
 
+// Split-bf16 forward / dX (see bf3_tile): the specialised 3-layer builds with obs dim <= 32 and
+// 64-row chunks -- net split, and both 32-wide nets in one 8-wave workgroup. The one definition:
+// the kernel folds on it, and the plan (ppo_rc.hip) sets g.bf3 and allocates the bf16 weight
+// images from it, applied to the instance row it chose.
+constexpr bool rc_is_bf3(int KT, int S0T, int NLT, int HWT, int CWT, int NW) {
+  return HWT == 16 * KT && NLT == 3 && S0T != 0 && (S0T > 0 ? S0T : -S0T) <= 8 && CWT == 64 && (NW == 4 || KT == 2);
+}
+
 // Shape specialisation: S0T (16-wide input k-steps / 4), NLT (layers per net), ACTT (hidden
 // activation), HWT (hidden width) fold the per-layer loop bounds, tile counts and the
 // activation switch at compile time; 0 / -1 = read them at run time (generic build).
@@ -448,10 +456,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   // to the bound); 0: generic (<= 16)
   constexpr int S0M = S0T > 0 ? S0T : (S0T < 0 ? -S0T : 16);
   const int s0 = S0T > 0 ? S0T : (D + 3) / 4;
-  // split-bf16 forward / dX (see bf3_tile): the specialised 3-layer builds with obs dim <= 32 and
-  // 64-row chunks -- net split, and both 32-wide nets in one 8-wave workgroup (the plan sets g.bf3
-  // for exactly these and allocates the bf16 weight images)
-  constexpr bool BF3 = (HWT == 16 * KT) && NLT == 3 && S0T != 0 && S0M <= 8 && CWT == 64 && (NW == 4 || KT == 2);
+  constexpr bool BF3 = rc_is_bf3(KT, S0T, NLT, HWT, CWT, NW);
   const bool gauss = DT >= 0 ? DT == 0 : !a.discrete;
   const bool has_ls = gauss && a.log_std_off >= 0;
   float am[4];  // action-slot masks of this lane group (Gaussian head)
@@ -1585,20 +1590,6 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
     else if (q == 1 && critic_slot) atomicAdd(a.prof + tid, sprof[tid]);
   }
 }
-
-// waves per workgroup (NW) and owned weight / bias slots per wave of each tile width
-// (generic builds; the shape-specialised ones size KW / KB to their exact item counts)
-constexpr int waves_for(int kt) { return kt == 2 ? 8 : 4; }
-constexpr int wslots_for(int kt) { return kt == 2 ? 5 : 16; }
-constexpr int bslots_for(int kt) { return kt == 2 ? 2 : 3; }
-// net split (4 waves, one net's items): up to 20 / 32 weight tiles and 8 vectors per net
-constexpr int wslots_ns(int kt) { return kt == 2 ? 5 : 8; }
-constexpr int bslots_ns() { return 2; }
-// generic both-nets build at 4 waves (<= 32-wide nets): up to 20 weight tiles (3-layer nets with
-// obs dim <= 32), 8 vectors
-constexpr int kNarrow4W = 5;
-constexpr int kNarrow4B = 2;
-
 
 }  // namespace rc
 }  // namespace ia

@@ -167,17 +167,21 @@ def supports_generator(venv, gen_algo) -> Tuple[bool, str]:
     return True, ""
 
 
-def ppo_path(pol: ActorCriticPolicy, nat, batch: int, rows: int, rc_gmax: int = 0) -> str:
-    """Which PPO kernel the engine would run (``"rc:g<G>x<nch>x<cw>:kt<KT>"`` or ``"lds"``)."""
+def _ppo_shape_args(pol: ActorCriticPolicy, nat, batch: int, rows: int, rc_gmax: int = 0) -> Dict[str, Any]:
+    """The shape / planning part of the ``engine_ppo_*`` argument dict (what the host plan reads)."""
     norm, pl, vl, act = _policy_nets(pol)
     discrete = isinstance(nat.action_space, spaces.Discrete)
     D = int(np.prod(nat.observation_space.shape))
     A = int(nat.action_space.n) if discrete else int(np.prod(nat.action_space.shape))
-    d = dict(D=D, A=A, discrete=int(discrete), pi_dims=[D] + [l.out_features for l in pl],
-             vf_dims=[D] + [l.out_features for l in vl], batch=int(batch), rows=int(rows),
-             log_std_off=0 if (hasattr(pol, "log_std") and not discrete) else -1, rc_gmax=int(rc_gmax),
-             hidden_act=int(act))
-    return ops.native().engine_ppo_path(d)
+    return dict(D=D, A=A, discrete=int(discrete), pi_dims=[D] + [l.out_features for l in pl],
+                vf_dims=[D] + [l.out_features for l in vl], batch=int(batch), rows=int(rows),
+                log_std_off=0 if (hasattr(pol, "log_std") and not discrete) else -1, rc_gmax=int(rc_gmax),
+                hidden_act=int(act))
+
+
+def ppo_path(pol: ActorCriticPolicy, nat, batch: int, rows: int, rc_gmax: int = 0) -> str:
+    """Which PPO kernel the engine would run (``"rc:g<G>x<nch>x<cw>:kt<KT>"`` or ``"lds"``)."""
+    return ops.native().engine_ppo_path(_ppo_shape_args(pol, nat, batch, rows, rc_gmax))
 
 
 class _FlatParams:
@@ -330,15 +334,12 @@ class DeviceGeneratorCore:
     def _ppo_args_static(self) -> Dict[str, Any]:
         algo: PPO = self.gen_algo
         fp = self.flat
-        pi_dims = [self.D] + [l.out_features for l in self.pi_layers]
-        vf_dims = [self.D] + [l.out_features for l in self.vf_layers]
-        d = dict(D=self.D, A=self.A, discrete=int(self.discrete), pi_dims=pi_dims, vf_dims=vf_dims,
-                 pi_w_off=[fp.offset(l.weight) for l in self.pi_layers], pi_b_off=[fp.offset(l.bias) for l in self.pi_layers],
+        d = _ppo_shape_args(algo.policy, self._native, algo.batch_size, self.T * self.N)
+        d.update(pi_w_off=[fp.offset(l.weight) for l in self.pi_layers], pi_b_off=[fp.offset(l.bias) for l in self.pi_layers],
                  vf_w_off=[fp.offset(l.weight) for l in self.vf_layers], vf_b_off=[fp.offset(l.bias) for l in self.vf_layers],
                  log_std_off=fp.offset(self.gen_algo.policy.log_std) if self.has_log_std else -1,
-                 hidden_act=int(self.hidden_act), params=fp.flat, grads=self.grads, exp_avg=self.exp_avg,
-                 exp_avg_sq=self.exp_avg_sq, n_params=fp.n, has_norm=int(self.pol_norm is not None),
-                 rows=self.T * self.N, batch=int(algo.batch_size), n_epochs=int(algo.n_epochs),
+                 params=fp.flat, grads=self.grads, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, n_params=fp.n,
+                 has_norm=int(self.pol_norm is not None), n_epochs=int(algo.n_epochs),
                  ent_coef=float(algo.ent_coef), vf_coef=float(algo.vf_coef), max_grad_norm=float(algo.max_grad_norm),
                  normalize_advantage=int(algo.normalize_advantage), adam_step=self.adam_step, stats=self.stats,
                  err=self._ppo_err.word,

@@ -4,7 +4,10 @@ Compiles each source for gfx950 with ``-Rpass-analysis=kernel-resource-usage`` (
 no object kept) and prints one markdown table row per kernel instance: VGPRs, AGPRs, SGPRs,
 scratch bytes per lane, occupancy (waves / SIMD) and static LDS. Usage::
 
-    python tools/kernel_resources.py csrc/kernels/ppo_rc.hip csrc/kernels/rollout.hip
+    python tools/kernel_resources.py csrc/kernels/ppo_rc_inst_a.hip csrc/kernels/rollout.hip
+
+Without arguments: every unit of the register-chained PPO update (``ppo_rc_inst_{a..f}.hip``,
+``ppo_rc.hip``).
 """
 
 from __future__ import annotations
@@ -60,4 +63,6 @@ def main(srcs):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or [os.path.join(ROOT, "csrc", "kernels", "ppo_rc.hip")])
+    # default: the PPO update -- the six instance units (ppo_rc_instances.h) and the prep kernel
+    main(sys.argv[1:] or [os.path.join(ROOT, "csrc", "kernels", f) for f in
+                          [f"ppo_rc_inst_{g}.hip" for g in "abcdef"] + ["ppo_rc.hip"]])
