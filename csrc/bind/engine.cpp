@@ -167,6 +167,34 @@ void reward_outnorm(py::dict d) {
   IA_HIP_CHECK2(ia::reward_outnorm_launch(a, ia_stream()));
 }
 
+void reward_retnorm(py::dict d) {
+  ia::RetNormArgs a{};
+  a.T = ival(d, "T");
+  a.N = ival(d, "N");
+  TORCH_CHECK(a.T >= 0 && a.N >= 0, "reward_retnorm: negative shape");
+  const int64_t rows = (int64_t)a.T * a.N;
+  // the kernel indexes every buffer by (t, n): check the sizes and dtypes here
+  auto sized = [&](const char* k, torch::ScalarType ty, int64_t numel) {
+    auto t = d[k].cast<torch::Tensor>();
+    TORCH_CHECK(t.scalar_type() == ty && t.numel() >= numel, "reward_retnorm: ", k, " has the wrong dtype or size");
+  };
+  a.env_rew = tptr<const float>(d, "env_rew");
+  a.dones = tptr<const float>(d, "dones");
+  a.boot = tptr<const float>(d, "boot");
+  a.rewards = tptr<float>(d, "rewards");
+  a.ret = tptr<double>(d, "ret");
+  a.rms = tptr<double>(d, "rms");
+  a.work = tptr<double>(d, "work");
+  for (const char* k : {"env_rew", "dones", "boot", "rewards"}) sized(k, torch::kFloat32, rows);
+  sized("ret", torch::kFloat64, a.N);
+  sized("rms", torch::kFloat64, 3);
+  sized("work", torch::kFloat64, rows);
+  a.gamma = fval(d, "gamma", 0.99);
+  a.eps = fval(d, "eps", 1e-8);
+  a.clip = fval(d, "clip", 10.0);
+  IA_HIP_CHECK2(ia::reward_retnorm_launch(a, ia_stream()));
+}
+
 // The shape and planning fields of PPOArgs (what ppo_rc_plan / ppo_lds_bytes read): the part of
 // the dict that engine_ppo_update, engine_ppo_plan, engine_ppo_path and engine_ppo_lds share.
 ia::PPOArgs ppo_shape_args(const py::dict& d) {
@@ -358,6 +386,7 @@ void register_engine(py::module& m) {
   m.def("engine_rollout_post", &rollout_post,
         "values, log-probs, TimeLimit bootstrap and learned reward of a rollout, all transitions in parallel");
   m.def("engine_reward_outnorm", &reward_outnorm, "NormalizedRewardNet output normalisation over a rollout");
+  m.def("engine_reward_retnorm", &reward_retnorm, "VecNormalize discounted-return reward normalisation over a rollout");
   m.def("engine_ppo_update", &ppo_update, "persistent PPO update / DP minibatch grads / apply");
   m.def("engine_ppo_path", &ppo_path, "kernel used by engine_ppo_update mode 0 (rc | lds)");
   m.def("engine_ppo_plan", &ppo_plan, "host plan of the register-chained PPO update: instance + launch geometry");

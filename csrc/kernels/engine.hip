@@ -163,15 +163,16 @@ __device__ __forceinline__ float reward_input(const RolloutPostArgs& a, float o,
 
 // (count, mean, biased var) of a <- a merged with b (Chan et al.; the update of
 // RunningNorm.update_stats for b = one step's batch). a empty: b exactly.
-__device__ __forceinline__ void chan_merge(float& n, float& m, float& v, float bn, float bm, float bv) {
-  if (bn <= 0.f) return;
-  if (n <= 0.f) {
+template <typename F>
+__device__ __forceinline__ void chan_merge(F& n, F& m, F& v, F bn, F bm, F bv) {
+  if (bn <= F(0)) return;
+  if (n <= F(0)) {
     n = bn;
     m = bm;
     v = bv;
     return;
   }
-  const float delta = bm - m, tot = n + bn;
+  const F delta = bm - m, tot = n + bn;
   m += delta * bn / tot;
   v = (v * n + bv * bn + delta * delta * n * bn / tot) / tot;
   n = tot;
@@ -281,6 +282,148 @@ __global__ __launch_bounds__(kOutNormThreads) void reward_outnorm_kernel(OutNorm
     else a.count[0] = state[2];
   }
 }
+
+// c after k host-order additions c = c + n (n a positive integer, c < 2^53), without walking
+// them: c and n are multiples of ulp(c), so additions are exact until c passes the next power of
+// two, and only that addition rounds. The running count of the returns' statistics is then
+// bitwise the host's at every step, however the steps are split over lanes and launches.
+__device__ __forceinline__ double count_after(double c, double n, int k) {
+  while (k > 0) {
+    int e;
+    frexp(c, &e);  // c in [2^(e-1), 2^e)
+    const double lim = ldexp(1.0, e);
+    int j = (int)fmin((lim - c) / n, (double)k);
+    while (j > 0 && c + (double)j * n > lim) --j;  // (the quotient may have rounded up)
+    c += (double)j * n;  // exact
+    k -= j;
+    if (k == 0) break;
+    c += n;  // rounds as the host's addition does
+    --k;
+  }
+  return c;
+}
+
+// VecNormalize(norm_obs=False) reward normalisation over a rollout (see RetNormArgs), sequential
+// in t on the host. Four phases per chunk of kRetNormChunk steps: (R) the discounted return of
+// every env, one wave per env: P_t = done_t ? 0 : gamma P_{t-1} + r_t is an affine map of
+// P_{t-1}, so lane l folds its run of steps, a 6-level prefix over the lanes gives each run's
+// carry-in and the lane replays its run from there, writing R[t][n] = gamma P_{t-1} + r_t;
+// (A) every step's batch moments of R[t][:] in parallel; (B) the Chan recurrence over the steps
+// as the same kind of scan on wave 0, INCLUSIVE: step t is normalised with the variance after
+// merging step t (reward_outnorm_kernel: before); (C) every reward in parallel. fp64 throughout
+// (the host wrapper's precision): the result is the host's up to the final fp32 rounding.
+constexpr int kRetNormThreads = 512;
+constexpr int kRetNormChunk = 4096;
+
+__global__ __launch_bounds__(kRetNormThreads) void reward_retnorm_kernel(RetNormArgs a) {
+  __shared__ double sm[kRetNormChunk], sv[kRetNormChunk];
+  __shared__ double state[3];  // (mean, var, count)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = a.N;
+  const double bn = (double)N;
+  if (tid == 0) {
+    state[0] = a.rms[0];
+    state[1] = a.rms[1];
+    state[2] = a.rms[2];
+  }
+  for (int t0 = 0; t0 < a.T; t0 += kRetNormChunk) {
+    const int nt = min(kRetNormChunk, a.T - t0);
+    const int per = (nt + 63) >> 6;
+    const int j0 = min(lane * per, nt), j1 = min(j0 + per, nt);
+    const int last = min((nt - 1) / per, 63);  // the lane whose run ends the chunk
+    // (R) returns
+    for (int n = wave; n < N; n += kRetNormThreads / 64) {
+      const float* r = a.env_rew + (size_t)t0 * N + n;
+      const float* d = a.dones + (size_t)t0 * N + n;
+      double A = 1.0, B = 0.0;  // this lane's run: P_out = A P_in + B
+      for (int j = j0; j < j1; ++j) {
+        const bool done = d[(size_t)j * N] > 0.5f;
+        A = done ? 0.0 : a.gamma * A;
+        B = done ? 0.0 : a.gamma * B + (double)r[(size_t)j * N];
+      }
+#pragma unroll
+      for (int k = 1; k < 64; k <<= 1) {  // inclusive prefix over lanes 0..l
+        const double oA = __shfl_up(A, k, 64), oB = __shfl_up(B, k, 64);
+        if (lane >= k) {
+          B = A * oB + B;
+          A = A * oA;
+        }
+      }
+      const double cA = __shfl_up(A, 1, 64), cB = __shfl_up(B, 1, 64);
+      double P = a.ret[n];
+      if (lane > 0) P = cA * P + cB;
+      for (int j = j0; j < j1; ++j) {
+        const double R = P * a.gamma + (double)r[(size_t)j * N];
+        a.work[(size_t)(t0 + j) * N + n] = R;
+        P = d[(size_t)j * N] > 0.5f ? 0.0 : R;
+      }
+      if (lane == last) a.ret[n] = P;
+    }
+    __syncthreads();
+    // (A) batch moments of each step's returns (RunningMeanStd.update: mean, biased var)
+    for (int j = tid; j < nt; j += kRetNormThreads) {
+      const double* x = a.work + (size_t)(t0 + j) * N;
+      double s = 0.0;
+      for (int n = 0; n < N; ++n) s += x[n];
+      const double bm = s / bn;
+      double q = 0.0;
+      for (int n = 0; n < N; ++n) {
+        const double dx = x[n] - bm;
+        q += dx * dx;
+      }
+      sm[j] = bm;
+      sv[j] = q / bn;
+    }
+    __syncthreads();
+    // (B) running variance after each step (replaces the step's batch variance in LDS)
+    if (wave == 0) {
+      double n = 0.0, m = 0.0, v = 0.0;  // this lane's run, folded (n = 0: identity)
+      for (int j = j0; j < j1; ++j) chan_merge(n, m, v, bn, sm[j], sv[j]);
+#pragma unroll
+      for (int k = 1; k < 64; k <<= 1) {
+        const double on = __shfl_up(n, k, 64), om = __shfl_up(m, k, 64), ov = __shfl_up(v, k, 64);
+        if (lane >= k) {
+          double pn = on, pm = om, pv = ov;
+          chan_merge(pn, pm, pv, n, m, v);
+          n = pn;
+          m = pm;
+          v = pv;
+        }
+      }
+      const double cn = __shfl_up(n, 1, 64), cm = __shfl_up(m, 1, 64), cv = __shfl_up(v, 1, 64);
+      double rn = state[2], rm = state[0], rv = state[1];
+      if (lane > 0) chan_merge(rn, rm, rv, cn, cm, cv);
+      rn = count_after(state[2], bn, j0);
+      for (int j = j0; j < j1; ++j) {
+        chan_merge(rn, rm, rv, bn, sm[j], sv[j]);
+        sv[j] = rv;
+      }
+      const double fn = __shfl(rn, last, 64), fm = __shfl(rm, last, 64), fv = __shfl(rv, last, 64);
+      if (lane == 0) {
+        state[0] = fm;
+        state[1] = fv;
+        state[2] = fn;
+      }
+    }
+    __syncthreads();
+    // (C) normalised, clipped rewards + TimeLimit bootstrap
+    const int n_el = nt * N;
+    for (int e = tid; e < n_el; e += kRetNormThreads) {
+      const int j = e / N;
+      const size_t i = (size_t)t0 * N + e;
+      double x = (double)a.env_rew[i] / sqrt(sv[j] + a.eps);
+      x = x < -a.clip ? -a.clip : (x > a.clip ? a.clip : x);
+      a.rewards[i] = (float)x + a.boot[i];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    a.rms[0] = state[0];
+    a.rms[1] = state[1];
+    a.rms[2] = state[2];
+  }
+}
+
 constexpr int kPostWaves = 8;  // waves per workgroup sharing one LDS image of the nets
 
 __global__ __launch_bounds__(64 * kPostWaves) void rollout_post_kernel(RolloutPostArgs a) {
@@ -378,6 +521,12 @@ hipError_t rollout_post_launch(const RolloutPostArgs& a, hipStream_t s) {
 hipError_t reward_outnorm_launch(const OutNormArgs& a, hipStream_t s) {
   if (a.T <= 0 || a.N <= 0) return hipSuccess;
   hipLaunchKernelGGL(reward_outnorm_kernel, dim3(1), dim3(kOutNormThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t reward_retnorm_launch(const RetNormArgs& a, hipStream_t s) {
+  if (a.T <= 0 || a.N <= 0) return hipSuccess;
+  hipLaunchKernelGGL(reward_retnorm_kernel, dim3(1), dim3(kRetNormThreads), 0, s, a);
   return hipGetLastError();
 }
 

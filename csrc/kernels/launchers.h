@@ -393,6 +393,22 @@ hipError_t rollout_launch(const RolloutArgs& a, hipStream_t s);
 size_t rollout_post_lds_bytes(const RolloutPostArgs& a);
 hipError_t rollout_post_launch(const RolloutPostArgs& a, hipStream_t s);
 hipError_t reward_outnorm_launch(const OutNormArgs& a, hipStream_t s);
+// VecNormalize(norm_obs=False, training=True) over a rollout, step by step as the host wrapper:
+// ret[n] = ret[n] * gamma + env_rew[t][n]; (mean, var, count) Chan-merged with the batch moments
+// of ret[0..N-1]; rewards[t][n] = clip(env_rew[t][n] / sqrt(var + eps), -clip, clip) + boot[t][n]
+// with the var AFTER that merge; ret[n] = 0 where dones[t][n]. fp64 state, as on the host.
+struct RetNormArgs {
+  int T, N;
+  const float* env_rew;  // [T][N]
+  const float* dones;    // [T][N] (> 0.5: episode end)
+  const float* boot;     // [T][N] TimeLimit bootstrap, added after the normalisation
+  float* rewards;        // [T][N] out
+  double* ret;           // [N] discounted return per env, updated in place
+  double* rms;           // [3] (mean, var, count) of the returns, updated in place
+  double* work;          // [T][N] scratch (the returns of every step)
+  double gamma, eps, clip;
+};
+hipError_t reward_retnorm_launch(const RetNormArgs& a, hipStream_t s);
 
 // ---- ppo_rc.hip: register-chained single-rank PPO update (falls back to ppo.hip)
 bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan);  // host only; false: outside the fast path

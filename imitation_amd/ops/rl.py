@@ -68,6 +68,64 @@ def explained_variance_from_moments(moments, rows: int) -> float:
     return float("nan") if var_r == 0 else float(1.0 - var_a / var_r)
 
 
+def return_normalize_reference(env_rew, dones, boot, ret, rms, gamma: float = 0.99, eps: float = 1e-8,
+                               clip: float = 10.0) -> torch.Tensor:
+    """Serial fp64 twin of :func:`return_normalize`: ``VecNormalize(norm_obs=False,
+    training=True).step_wait`` (``envs/vec_env.py``) applied to the ``[T, N]`` steps in order,
+    then the TimeLimit bootstrap. ``ret`` ``[N]`` and ``rms`` ``[3]`` = (mean, var, count), both
+    fp64, are updated in place; returns the fp32 rewards."""
+    import numpy as np
+
+    r = env_rew.detach().cpu().numpy().astype(np.float32, copy=False)
+    d = dones.detach().cpu().numpy() > 0.5
+    R = ret.detach().cpu().numpy().astype(np.float64)
+    mean, var, count = (float(x) for x in rms.detach().cpu().numpy().astype(np.float64))
+    out = np.empty(r.shape, np.float32)
+    for t in range(r.shape[0]):
+        R = R * gamma + r[t]
+        bm, bv, bc = np.mean(R), np.var(R), R.shape[0]  # RunningMeanStd.update
+        delta, tot = bm - mean, count + bc
+        m2 = var * count + bv * bc + np.square(delta) * count * bc / tot
+        mean, var, count = mean + delta * bc / tot, m2 / tot, tot
+        out[t] = np.clip(r[t] / np.sqrt(var + eps), -clip, clip).astype(np.float32)
+        R[d[t]] = 0.0
+    ret.copy_(torch.from_numpy(R))
+    rms.copy_(torch.tensor([mean, var, count], dtype=torch.float64))
+    return (torch.from_numpy(out) + boot.detach().cpu().float()).to(env_rew.device)
+
+
+def return_normalize(env_rew, dones, boot, ret, rms, gamma: float = 0.99, eps: float = 1e-8, clip: float = 10.0,
+                     out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SB3 ``VecNormalize(norm_obs=False)`` reward normalisation of a whole ``[T, N]`` rollout:
+    each reward divided by the running standard deviation of the discounted return (statistics
+    that already include its own step), clipped to ``±clip``, plus the TimeLimit bootstrap
+    ``boot``. ``ret`` ``[N]`` (the envs' discounted returns) and ``rms`` ``[3]`` = (mean, var,
+    count), both fp64, carry over between calls and are updated in place (a fresh
+    ``RunningMeanStd`` is (0, 1, 1e-4)). One ``reward_retnorm_kernel`` launch on the GPU
+    (csrc/kernels/engine.hip; ``out`` / ``work``: caller-owned ``[T, N]`` fp32 output and fp64
+    scratch), :func:`return_normalize_reference` on the CPU."""
+    from imitation_amd.ops import native, use_kernel
+
+    if ret.dtype != torch.float64 or rms.dtype != torch.float64:
+        raise TypeError("return_normalize: ret and rms must be float64")
+    T, N = env_rew.shape
+    if ret.numel() != N or rms.numel() != 3:
+        raise ValueError("return_normalize: ret must hold N values and rms (mean, var, count)")
+    if not use_kernel(env_rew):
+        res = return_normalize_reference(env_rew, dones, boot, ret, rms, gamma, eps, clip)
+        return res if out is None else out.copy_(res)
+    if not (ret.is_cuda and rms.is_cuda and ret.is_contiguous() and rms.is_contiguous()):
+        raise ValueError("return_normalize: ret and rms must be contiguous GPU tensors (they are updated in place)")
+    if out is None:
+        out = torch.empty(T, N, device=env_rew.device, dtype=torch.float32)
+    if work is None:
+        work = torch.empty(T, N, device=env_rew.device, dtype=torch.float64)
+    native().engine_reward_retnorm(dict(T=int(T), N=int(N), env_rew=env_rew.float().contiguous(),
+                                        dones=dones.float().contiguous(), boot=boot.float().contiguous(), rewards=out,
+                                        ret=ret, rms=rms, work=work, gamma=float(gamma), eps=float(eps), clip=float(clip)))
+    return out
+
+
 _M64 = (1 << 64) - 1
 
 

@@ -81,6 +81,30 @@ def resolve_hub_model(algo_name: str, env_name: str, organization: str = "HumanC
     )
 
 
+def install_hub_model(model_zip, algo_name: str, env_name: str, organization: str = "HumanCompatibleAI",
+                      hub=None) -> pathlib.Path:
+    """Copy ``model_zip`` to ``<hub or hub_dir()>/<organization>/<algo>-<env-with-dashes>/model.zip``
+    -- the first hub :func:`resolve_hub_model` searches, so ``<algo>-huggingface`` loads it
+    offline. The copy is renamed into place (a reader never sees a torn file; an installed
+    model is replaced). Returns the installed path."""
+    import shutil
+    import tempfile
+
+    root = pathlib.Path(hub) if hub is not None else hub_dir()
+    dst = root / organization / f"{algo_name}-{env_name_to_hub(env_name)}" / "model.zip"
+    dst.parent.mkdir(parents=True, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(dir=dst.parent, prefix="model.zip.", suffix=".tmp")
+    os.close(fd)
+    try:
+        shutil.copyfile(util.parse_path(model_zip), tmp)
+        os.replace(tmp, dst)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    return dst
+
+
 def _load_from_hub(algo_name: str, cls: Type) -> PolicyLoaderFn:
     def f(venv, env_name: str, organization: str = "HumanCompatibleAI"):
         return load_stable_baselines_model(cls, resolve_hub_model(algo_name, env_name, organization), venv).policy

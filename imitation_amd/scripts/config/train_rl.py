@@ -25,6 +25,8 @@ def train_rl_defaults():
     policy_save_interval = 10000  # timesteps between policy saves (<=0 disables)
     policy_save_final = True
     agent_path = None
+    engine = "host"  # "device": rollout + reward normalisation + PPO kernels (engine/rl.py); "auto": device if eligible
+    hub_install = False  # copy the final model.zip to where `expert.policy_type=ppo-huggingface` finds it offline
 
 
 @train_rl_ex.config
