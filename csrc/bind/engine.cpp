@@ -218,6 +218,11 @@ ia::PPOArgs ppo_shape_args(const py::dict& d) {
   a.rc_gmax = ival(d, "rc_gmax", 0);
   a.rc_cw = ival(d, "rc_cw", 0);
   a.rc_cus = ival(d, "rc_cus", 0);
+  a.rc_lean = ival(d, "rc_lean", 1);
+  // (planning only asks whether cycle counters were given: they keep the update on the full
+  // instance; engine_ppo_update validates the tensor and sets the pointer it launches with)
+  if (d.contains("prof") && !d["prof"].is_none())
+    a.prof = reinterpret_cast<unsigned long long*>(d["prof"].cast<torch::Tensor>().data_ptr());
   return a;
 }
 
@@ -305,7 +310,9 @@ py::dict ppo_plan(py::dict d) {
     return o;
   }
   const ia::PPORcGeo& g = plan.g;
-  const ia::PPORcRow& r = *plan.row;
+  // (the shape's full row: a lean twin that launches instead -- engine_ppo_row -- shares every
+  // constant reported here, so a plan reads the same whichever of the two runs it)
+  const ia::PPORcRow& r = *plan.full;
   o["path"] = ppo_path_of(g);
   o["instance"] = r.name;
   const std::pair<const char*, int> ints[] = {
@@ -318,6 +325,14 @@ py::dict ppo_plan(py::dict d) {
   o["lds_launch"] = plan.lds_launch;
   o["workspace_floats"] = plan.workspace_floats;
   return o;
+}
+
+// The instance-table row (ppo_rc_instances.h) that engine_ppo_update launches for this
+// configuration: the lean twin of the plan's "instance" for one row group without cycle counters
+// (unless rc_lean = 0), else that instance itself; "lds" off the fast path.
+std::string ppo_row(py::dict d) {
+  ia::PPORcPlan plan;
+  return ppo_plan_rc(d, plan) ? std::string(plan.row->name) : "lds";
 }
 
 size_t ppo_lds(py::dict d) { return ia::ppo_lds_bytes(ppo_shape_args(d)); }
@@ -389,6 +404,7 @@ void register_engine(py::module& m) {
   m.def("engine_reward_retnorm", &reward_retnorm, "VecNormalize discounted-return reward normalisation over a rollout");
   m.def("engine_ppo_update", &ppo_update, "persistent PPO update / DP minibatch grads / apply");
   m.def("engine_ppo_path", &ppo_path, "kernel used by engine_ppo_update mode 0 (rc | lds)");
+  m.def("engine_ppo_row", &ppo_row, "instance-table row that engine_ppo_update mode 0 runs (lean or full; lds off the fast path)");
   m.def("engine_ppo_plan", &ppo_plan, "host plan of the register-chained PPO update: instance + launch geometry");
   m.def("engine_ppo_lds", &ppo_lds, "LDS bytes the PPO kernel needs for a configuration");
 }

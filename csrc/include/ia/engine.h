@@ -174,6 +174,9 @@ struct PPOArgs {
   unsigned long long* prof;  // optional [10] cycle counters per phase
   int rc_gmax;   // mode 0 fast path: max cooperating workgroups per minibatch (0 = default kMaxRcGroups)
   int rc_cw;     // mode 0 fast path: rows per chunk override (0 = 64 for <= 32-wide nets, 32 otherwise)
+  // mode 0 fast path: 1 = a single-row-group plan (G == 1) without cycle counters (prof == nullptr)
+  // takes the lean instance of its shape where the table has one; 0 = always the full instance
+  int rc_lean;
   // fail-fast for the cooperating workgroups (mode 0 fast path): a bounded spin that gives up
   // ORs 1 into *err (persistent, host-checked; may be null) besides the per-launch flag
   unsigned* err;
@@ -236,6 +239,7 @@ struct PPORcRow {
   const char* name;
   int ns;  // net-split build (one net per workgroup)
   int KT, KW, KB, S0T, NLT, ACTT, HWT, CWT, DT, NW;
+  int LEAN;  // single-row-group build: no partial exchange, no cycle counters (G == 1, prof == nullptr only)
   void (*kernel)(PPOArgs, PPORcGeo);
 };
 
@@ -244,6 +248,7 @@ struct PPORcRow {
 struct PPORcPlan {
   PPORcGeo g;           // geometry incl. xchg2 / xcd (workspace pointers unset)
   const PPORcRow* row;  // the instance that runs it
+  const PPORcRow* full;  // the shape's full row: row itself, or the twin of a lean row
   size_t lds_bytes;     // LDS the geometry needs
   size_t lds_launch;    // LDS the launch asks for (padded to keep cooperating workgroups one per CU)
   unsigned grid, block;

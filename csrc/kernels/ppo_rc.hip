@@ -167,11 +167,13 @@ static bool rc_row_bf3(const PPORcRow& r) { return rc_is_bf3(r.KT, r.S0T, r.NLT,
 // The instance that runs a shape: the first row whose compile-time constants all agree with it
 // (a constant the row leaves to run time -- ppo_rc_kernel.h, "Shape specialisation" -- agrees
 // with anything), so a row is never chosen for a shape its constants do not fit. nullptr: no
-// scratch-free build runs this shape. bf3_ok false passes over the split-bf16 rows.
-static const PPORcRow* rc_select(const PPOArgs& a, int kt, int cw, bool ns, bool bf3_ok) {
+// scratch-free build runs this shape. bf3_ok false passes over the split-bf16 rows, lean_ok
+// false over the lean ones (a lean row precedes its full twin, so with lean_ok the twin of the
+// row chosen without it -- or that row again -- comes back).
+static const PPORcRow* rc_select(const PPOArgs& a, int kt, int cw, bool ns, bool bf3_ok, bool lean_ok) {
   const int s0 = (a.D + 3) / 4;
   for (const PPORcRow& r : kRcRows) {
-    bool ok = r.ns == (int)ns && r.KT == kt && (r.CWT <= 0 || r.CWT == cw);
+    bool ok = r.ns == (int)ns && r.KT == kt && (r.CWT <= 0 || r.CWT == cw) && (lean_ok || !r.LEAN);
     ok = ok && (r.NLT <= 0 || (a.n_pi == r.NLT && a.n_vf == r.NLT));
     if (r.HWT > 0) {
       for (int l = 1; l < a.n_pi; ++l) ok = ok && a.pi_dims[l] == r.HWT;
@@ -242,14 +244,14 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan) {
   // the instance. No row: the generic 8-wave both-nets build (256 registers per wave) and the
   // generic 64-wide builds (owned items + vectors at run-time shapes) need scratch and are not
   // compiled, so 64-wide nets outside the [64, 64] families take the LDS kernel
-  const PPORcRow* row = rc_select(a, KT, cw, ns, env_bf3);
+  const PPORcRow* row = rc_select(a, KT, cw, ns, env_bf3, false);
   if (row == nullptr) return reject(4);
   if (row->CWT <= 0) {  // run-time chunk width: at most the rows the net's row-tile waves cover
     const int cover = 16 * (ns ? row->NW : row->NW / 2);
     if (cw > cover) cw = cover;
     if (a.batch % cw != 0) cw = 16;
   }
-  plan.row = row;
+  plan.row = plan.full = row;
   g.nw = row->NW;
   g.ns = ns ? 1 : 0;
   g.bf3 = rc_row_bf3(*row) ? 1 : 0;
@@ -273,6 +275,13 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan) {
   g.cw = cw;
   g.G = G;
   g.nch = chunks / G;
+  // one row group, no cycle counters: the lean twin of the row, where the table has one (the
+  // same constants, so everything planned from the row stays as it is; PPOArgs::rc_lean = 0
+  // keeps the full row)
+  if (G == 1 && a.rc_lean != 0 && a.prof == nullptr) {
+    const PPORcRow* lean = rc_select(a, KT, cw, ns, env_bf3, true);
+    if (lean != nullptr && lean->LEAN && lean->NW == row->NW && lean->CWT == row->CWT) plan.row = lean;
+  }
   int off = 0;
   auto take = [&](int n) {
     const int o = off;

@@ -41,7 +41,17 @@
 // bit-identical update to its own LDS copy of the parameters; there is one grid-wide
 // wait per minibatch and no parameter broadcast. The spin is bounded (timeout flag).
 //
-// barriers / minibatch: [fwd+loss+bwd chain] B1 [dW items] (exchange) [|g|^2] B2 [clip, Adam] B3
+// barriers / minibatch:
+//   B3 [operand prefetch] [fwd+loss+bwd chain] B1 [dW items] (exchange) [|g|^2] B2 [clip, Adam] B3
+// * Operand prefetch (PREF, the 32-wide split-bf16 builds at one wave per SIMD): right after B3 a
+//   row wave reads all of its net's forward / transposed weight operands, the bias vectors and
+//   log_std into registers in one block -- they change only in Adam -- so no weight read queues
+//   behind the chain's image stores, and the chunks of a minibatch reuse the registers.
+// * Adam's step scalars (bias corrections, step size) do not depend on the gradient and are
+//   formed before B2 or, under the net split, while the other net's |g|^2 is on its way (kEarly);
+//   only the clip coefficient follows the total.
+// * LEAN instances (template flag) are the G == 1 builds without the exchange block and without
+//   the a.prof cycle counters; see the template's comment and ppo_rc_instances.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -348,6 +358,13 @@ __device__ __forceinline__ f4 bf3_tile(const lbf* a, int lo_off, bf16x8 bh, bf16
   return mfma_bf16(al, bh, acc);
 }
 
+// the same triple with the A operand already in registers (operand prefetch, PREF builds)
+__device__ __forceinline__ f4 bf3_mm(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f4 acc) {
+  acc = mfma_bf16(ah, bh, acc);
+  acc = mfma_bf16(ah, bl, acc);
+  return mfma_bf16(al, bh, acc);
+}
+
 // Geometry of layer l's images: forward Wf [16-padded dout rows][pos(in)] (K = 32 for layer 0,
 // 16 KT for hidden inputs), transposed Wt [16-padded din rows][pos_h(out)] (layers >= 1; K = 32 for
 // the head's <= 16 outputs, 16 KT otherwise); lo image right after hi.
@@ -425,9 +442,16 @@ constexpr bool rc_is_bf3(int KT, int S0T, int NLT, int HWT, int CWT, int NW) {
 // (it < KW; a 16 x 16 tile, 4 elements per lane) and bias / log_std items n_witems + w + ib * NW
 // (ib < KB; one element per lane), so the owned state is 12 KW + 3 KB floats per lane and
 // every slot's kind is known at compile time.
-template <int KT, int KW, int KB, int S0T, int NLT, int ACTT, int HWT, int CWT, int DT, int NW>
+// LEAN: 1 = the build for one row group (G == 1) without cycle counters: G folds to 1, the
+// exchange block (publish, both arrivals, one- / two-level sums, stash, slab pointers, ids / xg)
+// and every a.prof stamp are compiled out -- otherwise they cost the HalfCheetah instance ~500
+// SGPR spills into VGPR lanes although none of it runs. nch stays a run-time value. The plan
+// (ppo_rc.hip rc_select) takes a lean row only for G == 1 and a.prof == nullptr.
+template <int KT, int KW, int KB, int S0T, int NLT, int ACTT, int HWT, int CWT, int DT, int NW, int LEAN = 0>
 __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) {
   constexpr int KI = KW + KB;
+  constexpr bool kLean = LEAN != 0;
+  unsigned long long* const prof = kLean ? nullptr : a.prof;  // (lean: every stamp folds away)
   constexpr int kThreads = 64 * NW;
   constexpr int kWaves = NW;
   constexpr int kHalf = NW / 2;  // row-tile waves per net
@@ -445,7 +469,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   const int q = ns ? (bid & 1) : w / kHalf;  // 0 actor, 1 critic
   const int gw = ns ? w : w % kHalf;         // row tile
   const int grp = ns ? (bid >> 1) : bid;     // row group
-  const int G = g.G, nch = g.nch, cw = CWT > 0 ? CWT : g.cw;
+  const int G = kLean ? 1 : g.G, nch = g.nch, cw = CWT > 0 ? CWT : g.cw;
   const int CH = G * nch;
   const int Bg = CH * cw;  // minibatch rows
   const int RT = cw / 16;
@@ -727,7 +751,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   // stash, which borrows the activation images -- the layer-0 input image included -- during
   // the exchange)
   constexpr bool PREC = KW <= 8;
-  const bool pre = PREC && (ns || G > 1) && g.xstash < 0;
+  const bool pre = PREC && (ns || G > 1) && (kLean || g.xstash < 0);
   float xpre[PREC ? S0M : 1];
 #pragma unroll
   for (int s = 0; s < (PREC ? S0M : 1); ++s) xpre[s] = 0.f;
@@ -736,9 +760,67 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       if (pre && rows_wave && k + 1 < K) norm_rows(((k + 1) & 1) * 128, xpre);
   };
 
+  // Adam's per-step scalars: none depends on the gradient, so they are formed off the chain --
+  // after this net's |g|^2 is published, while the other net's is on its way (net split), or
+  // before B2 -- and only coef is left behind the total (kEarly; the 12 / 14-slot builds have
+  // no registers to carry them across the wait and form them behind it, as before)
+  constexpr bool kEarly = KW <= 8;
+  float step_size = 0.f, inv_bc2s = 0.f;
+  auto adam_scalars = [&]() {
+    step += 1.f;
+    b1t *= a.beta1;
+    b2t *= a.beta2;
+    step_size = a.lr / (1.f - b1t);
+    inv_bc2s = 1.f / sqrtf(1.f - b2t);
+  };
+
+  // Operand prefetch (PREF: the 32-wide split-bf16 builds, which have the registers): the weight
+  // images and bias vectors change only in Adam, between the hand-off and B3, so right after B3
+  // a row wave reads ALL of its net's forward (10 x b128) and transposed (8 x b128) operands and
+  // the bias vectors in one block, and every chunk of the minibatch feeds its MFMAs from those
+  // registers. Read next to their MFMAs instead, each ds_read_b128 queues behind the image
+  // stores of the layer before it (the LDS queue is in order) and is waited for at once: about
+  // ten exposed LDS round trips per chunk. pwf[l][t]: forward tile t of layer l (hi, lo);
+  // pwt[l][u]: transposed tile u of layer l >= 1; pbs[l][t]: bias of tile t; pls: the log-std
+  // vector of the Gaussian loss (also rewritten only by Adam).
+  constexpr bool PREF = BF3 && KT == 2 && NW == 4;  // (one wave per SIMD: the 512-entry file)
+  constexpr int PL = PREF ? NLT : 1, PT = PREF ? KT : 1;
+  bf16x8 pwf[PL][PT][2], pwt[PL][PT][2];
+  f4 pbs[PL][PT];
+  f4 pls = {0.f, 0.f, 0.f, 0.f};
+
   for (int k = 0; k < K; ++k) {
-    unsigned long long t0 = a.prof ? clock64() : 0;
+    unsigned long long t0 = prof ? clock64() : 0;
     const int nb = (k & 1) * 128;  // norm buffer of minibatch k
+    if constexpr (PREF) {
+      if (rows_wave) {
+        pls = *(const lf4*)(L + g.ls_off + 4 * kk);
+#pragma unroll
+        for (int l = 0; l < PL; ++l) {
+          const LG y = LY(l);
+          const bool last = l == PL - 1;
+          const int kin = l == 0 ? 32 : 16 * KT;
+          const int rows = (y.dout + 15) & ~15;
+          const lbf* wf = (const lbf*)(L + WF(l)) + r16 * bf3_ld(kin) + 8 * kk;
+#pragma unroll
+          for (int t = 0; t < PT; ++t) {
+            if (last && t > 0) continue;  // head: one output tile
+            pwf[l][t][0] = *(const lbf8*)(wf + 16 * t * bf3_ld(kin));
+            pwf[l][t][1] = *(const lbf8*)(wf + 16 * t * bf3_ld(kin) + rows * bf3_ld(kin));
+            pbs[l][t] = *(const lf4*)(L + y.b + 16 * t + 4 * kk);
+          }
+          if (l == 0) continue;
+          const int kout = last ? 32 : 16 * KT;
+          const int trows = (y.din + 15) & ~15;
+          const lbf* wt_img = (const lbf*)(L + WT(l)) + r16 * bf3_ld(kout) + 8 * kk;
+#pragma unroll
+          for (int u2 = 0; u2 < PT; ++u2) {
+            pwt[l][u2][0] = *(const lbf8*)(wt_img + 16 * u2 * bf3_ld(kout));
+            pwt[l][u2][1] = *(const lbf8*)(wt_img + 16 * u2 * bf3_ld(kout) + trows * bf3_ld(kout));
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int it = 0; it < KW; ++it) gg[it] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -757,7 +839,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
           pre_v = g.mom[(size_t)(k + 2) * 128 + 64 + nc];
         }
       }
-      unsigned long long c0 = a.prof ? clock64() : 0;
+      unsigned long long c0 = prof ? clock64() : 0;
       if (rows_wave) {
         // ---------------- normalised input: B operand of layer 0 (natural K order 4s + kk)
         // (chunk 0 of minibatch k > 0 under the exchange / net split: done in minibatch k-1's
@@ -790,7 +872,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
               if (s < s0) img_store(L, h0, cs, 4 * s + kk, row, xb[s]);
           }
         }
-        unsigned long long c1 = a.prof ? clock64() : 0;
+        unsigned long long c1 = prof ? clock64() : 0;
         // ---------------- forward (registers)
         f4 hreg[kL - 1][KT];  // outputs of hidden layers (C layout), kept for act'
         f4 head = {0.f, 0.f, 0.f, 0.f};
@@ -825,8 +907,11 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
               bf16x8 bh, bl;
               split8(v, bh, bl);
 #pragma unroll
-              for (int t = 0; t < KT; ++t)
-                if (t < tout) acc[t] = bf3_tile(wf + 16 * t * bf3_ld(kin) + 32 * ks, rows * bf3_ld(kin), bh, bl, acc[t]);
+              for (int t = 0; t < KT; ++t) {
+                if (t >= tout) continue;
+                if constexpr (PREF) acc[t] = bf3_mm(pwf[PREF ? l : 0][PREF ? t : 0][0], pwf[PREF ? l : 0][PREF ? t : 0][1], bh, bl, acc[t]);
+                else acc[t] = bf3_tile(wf + 16 * t * bf3_ld(kin) + 32 * ks, rows * bf3_ld(kin), bh, bl, acc[t]);
+              }
             }
           } else if (l == 0 && KT > 2) {  // 64-wide: two tiles' operands at a time (register budget)
 #pragma unroll
@@ -895,7 +980,9 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
           for (int t = 0; t < KT; ++t) {
             if (t >= tout) continue;
             const int o0 = 16 * t + 4 * kk;
-            const f4 bb = *(const lf4*)(L + y.b + o0);
+            f4 bb;
+            if constexpr (PREF) bb = pbs[PREF ? l : 0][PREF ? t : 0];
+            else bb = *(const lf4*)(L + y.b + o0);
             f4 v;
             v.x = acc[t].x + bb.x;
             v.y = acc[t].y + bb.y;
@@ -920,7 +1007,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
             }
           }
         }
-        unsigned long long c2 = a.prof ? clock64() : 0;
+        unsigned long long c2 = prof ? clock64() : 0;
         // ---------------- loss -> dZ of the head (C layout, tile 0)
         f4 dz = {0.f, 0.f, 0.f, 0.f};
         const LG yh = LY(nl - 1);
@@ -938,7 +1025,9 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
             // log_std 0, action 0 and mean 0 (zero weight rows), so zs = 0 there and only the
             // constant term needs the slot mask am[j]
             float part = 0.f;
-            const f4 ls4 = *(const lf4*)(L + g.ls_off + 4 * kk);
+            f4 ls4;
+            if constexpr (PREF) ls4 = pls;
+            else ls4 = *(const lf4*)(L + g.ls_off + 4 * kk);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float lsv = ls4[j];
@@ -1019,7 +1108,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
           }
           dz = {kk == 0 ? a.vf_coef * 2.f * d * invB : 0.f, 0.f, 0.f, 0.f};
         }
-        unsigned long long c3 = a.prof ? clock64() : 0;
+        unsigned long long c3 = prof ? clock64() : 0;
         // ---------------- backward chain: store dZ_l, bias partials, dZ_{l-1} = W_l^T dZ_l * act'
         f4 dzc[KT];
         dzc[0] = dz;
@@ -1081,8 +1170,11 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
               bf16x8 bh, bl;
               split8(v, bh, bl);
 #pragma unroll
-              for (int u2 = 0; u2 < KT; ++u2)
-                if (u2 < tin) accb[u2] = bf3_tile(wt_img + 16 * u2 * bf3_ld(kout) + 32 * ks, trows * bf3_ld(kout), bh, bl, accb[u2]);
+              for (int u2 = 0; u2 < KT; ++u2) {
+                if (u2 >= tin) continue;
+                if constexpr (PREF) accb[u2] = bf3_mm(pwt[PREF ? l : 0][PREF ? u2 : 0][0], pwt[PREF ? l : 0][PREF ? u2 : 0][1], bh, bl, accb[u2]);
+                else accb[u2] = bf3_tile(wt_img + 16 * u2 * bf3_ld(kout) + 32 * ks, trows * bf3_ld(kout), bh, bl, accb[u2]);
+              }
             }
           } else if constexpr (KT <= 2) {
 #pragma unroll
@@ -1122,7 +1214,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
 #pragma unroll
           for (int u2 = 0; u2 < KT; ++u2) dzc[u2] = nd[u2];
         }
-        if (a.prof && lane == 0 && gw == 0) {
+        if (prof && lane == 0 && gw == 0) {
           const unsigned long long c4 = clock64();
           const int pb = q == 1 ? 7 : 3;
           sprof[pb + 0] += c1 - c0;
@@ -1131,9 +1223,9 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
           sprof[pb + 3] += c4 - c3;
         }
       }
-      const unsigned long long cb0 = a.prof ? clock64() : 0;
+      const unsigned long long cb0 = prof ? clock64() : 0;
       __syncthreads();  // B1: H / dZ images, bias and log-std partials of this chunk complete
-      const unsigned long long cb1 = a.prof ? clock64() : 0;
+      const unsigned long long cb1 = prof ? clock64() : 0;
       // Chan merge for minibatch k+1 (one lane per feature, wave 7), off the chain's critical
       // path; minibatch k reads the other half of the double-buffered normaliser image
       if (ch == 0 && norm_lane && k + 1 < K) {
@@ -1180,17 +1272,17 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
           bg[ib] += gval * b_okf[ib];
         }
       }
-      if (a.prof && tid == 0) {
+      if (prof && tid == 0) {
         sprof[11] += cb1 - cb0;
         sprof[12] += clock64() - cb1;
       }
       if (rows_wave) cur = nxt;
       if (ch + 1 < nch) __syncthreads();  // images are rewritten by the next chunk
     }
-    unsigned long long t1 = a.prof ? clock64() : 0;
+    unsigned long long t1 = prof ? clock64() : 0;
 
     // ---------------- cross-workgroup exchange of the partials (G > 1)
-    if (G > 1) {
+    if constexpr (!kLean) if (G > 1) {
       // owned slots as one list: weight tiles, then bias / log_std vectors ({g, 0, 0, 0})
       int ids[KI];
       f4 xg[KI];
@@ -1210,10 +1302,10 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
         if (ids[it] < 0) continue;
         st_sc1_x4(slab + ((size_t)grp * n_items + ids[it]) * 256 + lane * 4, xg[it]);
       }
-      const unsigned long long e0 = a.prof ? clock64() : 0;
+      const unsigned long long e0 = prof ? clock64() : 0;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      const unsigned long long e1 = a.prof ? clock64() : 0;
+      const unsigned long long e1 = prof ? clock64() : 0;
       if (tid == 0 && !stall) atomicAdd(arrive, 1u);
       pre_rows(k);
       if (tid == 0) {
@@ -1228,7 +1320,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
         }
       }
       __syncthreads();
-      const unsigned long long e2 = a.prof ? clock64() : 0;
+      const unsigned long long e2 = prof ? clock64() : 0;
       if (g.xchg2) {
         // Two-level exchange (large G): slot it of every wave is reduced by workgroup
         // it % G, so each wave of each workgroup sums ~KI / G of its slots over the G
@@ -1358,7 +1450,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
 #pragma unroll
       for (int ib = 0; ib < KB; ++ib)
         if (ids[KW + ib] >= 0) bg[ib] = xg[KW + ib].x;
-      if (a.prof && tid == 0) {
+      if (prof && tid == 0) {
         sprof[13] += e1 - e0;
         sprof[14] += e2 - e1;
         sprof[15] += clock64() - e2;
@@ -1386,8 +1478,9 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       for (int j = 0; j < A; ++j) sl += has_ls ? L[g.ls_off + j] : 0.f;
       st_ent += -(sl + A * (0.5f + c_half_log2pi));
     }
+    if (kEarly && !ns) adam_scalars();
     __syncthreads();  // B2: all gradients formed
-    unsigned long long t2 = a.prof ? clock64() : 0;
+    unsigned long long t2 = prof ? clock64() : 0;
 
     // ---------------- clip_grad_norm_ + Adam on the owned items (W/b/log_std in LDS)
     float tot = 0.f;
@@ -1398,13 +1491,17 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       // the high word; MI355X_MICROARCH inter-workgroup visibility: 8-B agent atomics both
       // sides), polled by the other workgroup; summed actor + critic in both workgroups so
       // that they apply the identical clip
-      const unsigned long long x0 = a.prof ? clock64() : 0;
+      const unsigned long long x0 = prof ? clock64() : 0;
       unsigned long long* xs = reinterpret_cast<unsigned long long*>(g.sync + 8);
       const unsigned long long tag = (unsigned long long)(unsigned)(k + 1) << 32;
       if (tid == 0 && !stall) __hip_atomic_store(xs + q, tag | __float_as_uint(tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (G == 1) pre_rows(k);  // (G > 1: done in the arrival wait)
+      // the first poll is in flight under pre_rows and the Adam scalars
+      unsigned long long o = 0;
+      if (kEarly && tid == 0) o = __hip_atomic_load(xs + (1 - q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (G == 1) pre_rows(k);      // (G > 1: done in the arrival wait)
+      if (kEarly) adam_scalars();  // (in the shadow of the other net's publish-to-seen latency)
       if (tid == 0) {
-        unsigned long long o = __hip_atomic_load(xs + (1 - q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!kEarly) o = __hip_atomic_load(xs + (1 - q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unsigned spins = 0;
         while ((o >> 32) != (unsigned long long)(unsigned)(k + 1)) {
           __builtin_amdgcn_s_sleep(1);
@@ -1419,17 +1516,14 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       }
       __syncthreads();
       tot = L[g.red_off + 48];
-      if (a.prof && tid == 0) sprof[16] += clock64() - x0;  // (net split: the |g|^2 hand-off)
+      if (prof && tid == 0) sprof[16] += clock64() - x0;  // (net split: the |g|^2 hand-off)
     }
     // (stamps straight into LDS: no live registers; not in the full-register-file builds)
     constexpr bool kProfAdam = KW <= 8;
-    if (kProfAdam && a.prof && tid == 0) sprof[17] -= clock64();
+    if (kProfAdam && prof && tid == 0) sprof[17] -= clock64();
+    // (only coef depends on the total: step_size / inv_bc2s were formed before the wait)
+    if (!kEarly) adam_scalars();
     const float coef = fminf(1.f, a.max_grad_norm / (sqrtf(tot) + 1e-6f));
-    step += 1.f;
-    b1t *= a.beta1;
-    b2t *= a.beta2;
-    const float step_size = a.lr / (1.f - b1t);
-    const float inv_bc2s = 1.f / sqrtf(1.f - b2t);
     const float b1 = a.beta1, b2 = a.beta2, eps = a.adam_eps;
     // torch Adam: p -= step_size * m / (sqrt(v) / sqrt(1 - b2^t) + eps), on v_sqrt / v_rcp
     // (~1 ulp each). All of this wave's parameter reads are issued before any write
@@ -1493,13 +1587,13 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       const float denom = __builtin_amdgcn_sqrtf(bv[ib]) * inv_bc2s + eps;
       L[b_addr[ib]] = bval[ib] - step_size * bm[ib] * __builtin_amdgcn_rcpf(denom);
     }
-    if (kProfAdam && a.prof && tid == 0) {
+    if (kProfAdam && prof && tid == 0) {
       const unsigned long long a1 = clock64();
       sprof[17] += a1;
       sprof[18] -= a1;
     }
     __syncthreads();  // B3: parameters updated
-    if (a.prof && tid == 0) {
+    if (prof && tid == 0) {
       const unsigned long long t3 = clock64();
       sprof[0] += t1 - t0;
       sprof[1] += t2 - t1;
@@ -1583,11 +1677,11 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   if (shared_wb && tid == 0) a.adam_step[0] = step;
   // (stats barrier above orders the LDS). Net split: the critic workgroup owns the critic
   // row-tile counters [7..10] (the actor's are zero there), added atomically
-  if (a.prof && tid < 20) {
+  if (prof && tid < 20) {
     const bool critic_slot = tid >= 7 && tid <= 10;
-    if (!ns) a.prof[tid] += sprof[tid];
-    else if (q == 0 && !critic_slot) a.prof[tid] += sprof[tid];
-    else if (q == 1 && critic_slot) atomicAdd(a.prof + tid, sprof[tid]);
+    if (!ns) prof[tid] += sprof[tid];
+    else if (q == 0 && !critic_slot) prof[tid] += sprof[tid];
+    else if (q == 1 && critic_slot) atomicAdd(prof + tid, sprof[tid]);
   }
 }
 

@@ -344,7 +344,10 @@ class DeviceGeneratorCore:
                  normalize_advantage=int(algo.normalize_advantage), adam_step=self.adam_step, stats=self.stats,
                  err=self._ppo_err.word,
                  # fail-fast knobs of the cooperating-workgroup kernel (tests force a timeout)
-                 spin_limit=0, debug_stall=0)  # (tests set these two in _ppo_static)
+                 spin_limit=0, debug_stall=0,  # (tests set these two in _ppo_static)
+                 # one row group without cycle counters runs the lean kernel instance of its shape
+                 # (csrc/kernels/ppo_rc_instances.h); 0 keeps the full one (bitwise the same update)
+                 rc_lean=1)
         opt = algo.policy.optimizer
         g = opt.param_groups[0]
         d.update(beta1=float(g.get("betas", (0.9, 0.999))[0]), beta2=float(g.get("betas", (0.9, 0.999))[1]),
