@@ -337,6 +337,22 @@ std::string ppo_row(py::dict d) {
 
 size_t ppo_lds(py::dict d) { return ia::ppo_lds_bytes(ppo_shape_args(d)); }
 
+// The dW operand fragments of an fp32 [rows][feats] matrix as the register-chained update's image
+// helpers store and read them back (ppo_rc.hip ppo_image_probe_kernel): int16 bf16 bit patterns
+// [2 (hi, lo)][feats / 16][max(rows, 32) / 32][64 lanes][8].
+torch::Tensor ppo_image_probe(torch::Tensor x, int mode) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat32 && x.dim() == 2 && x.is_contiguous(),
+              "engine_ppo_image_probe: a contiguous fp32 [rows][features] device matrix");
+  const int rows = (int)x.size(0), feats = (int)x.size(1);
+  TORCH_CHECK(rows > 0 && rows <= 64 && rows % 16 == 0 && feats > 0 && feats <= 64 && feats % 16 == 0,
+              "engine_ppo_image_probe: rows and features multiples of 16, at most 64");
+  TORCH_CHECK(mode == 0 || mode == 1, "engine_ppo_image_probe: mode 0 (packed store) or 1 (per element)");
+  auto out = torch::zeros({2, feats / 16, (rows > 32 ? 64 : 32) / 32, 64, 8}, x.options().dtype(torch::kInt16));
+  IA_HIP_CHECK2(ia::ppo_image_probe_launch(x.data_ptr<float>(), rows, feats, mode,
+                                           reinterpret_cast<unsigned short*>(out.data_ptr<int16_t>()), ia_stream()));
+  return out;
+}
+
 }  // namespace
 
 // One DAgger-collector env step (mode 0) or reset of every env (mode 1); see dagger.hip.
@@ -407,4 +423,6 @@ void register_engine(py::module& m) {
   m.def("engine_ppo_row", &ppo_row, "instance-table row that engine_ppo_update mode 0 runs (lean or full; lds off the fast path)");
   m.def("engine_ppo_plan", &ppo_plan, "host plan of the register-chained PPO update: instance + launch geometry");
   m.def("engine_ppo_lds", &ppo_lds, "LDS bytes the PPO kernel needs for a configuration");
+  m.def("engine_ppo_image_probe", &ppo_image_probe,
+        "dW operand fragments of a matrix through the PPO update's split-bf16 image store and transposed reads (test hook)");
 }

@@ -198,7 +198,6 @@ struct PPORcGeo {
   int h_off[2][kWaveMaxLayers], ldh[2][kWaveMaxLayers];  // ldh / ldz: floats per image column
   int z_off[2][kWaveMaxLayers], ldz[2][kWaveMaxLayers], db_off[2][kWaveMaxLayers];
   int ls_off, lsp_off, nm_off, red_off, param_lds;
-  int zero_off;  // 64 floats of zeros (never written): operand of the padding dW items
   int trash_off;   // 64 floats: Adam target of padding elements
   int lds_floats;  // whole image size (zeroed at kernel start)
   int n_items;
@@ -207,7 +206,6 @@ struct PPORcGeo {
   int dp;                  // padded obs row stride of xraw
   int kt;                  // 16-wide tiles per hidden layer (2: width <= 32, 4: width <= 64)
   int cw;                  // rows per chunk (one fwd/bwd pass of a workgroup)
-  int ksteps;              // 32-row K-steps of a dW tile (split-bf16 images padded to >= 32 rows)
   int bf3;                 // split-bf16 forward / dX weight images (ppo_rc_kernel.h bf3_tile)
   int wf_off[2][kWaveMaxLayers], wt_off[2][kWaveMaxLayers];  // their offsets (floats; hi then lo)
   int nch;                 // chunks per workgroup per minibatch

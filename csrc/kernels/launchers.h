@@ -413,6 +413,9 @@ hipError_t reward_retnorm_launch(const RetNormArgs& a, hipStream_t s);
 // ---- ppo_rc.hip: register-chained single-rank PPO update (falls back to ppo.hip)
 bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan);  // host only; false: outside the fast path
 hipError_t ppo_rc_launch(const PPOArgs& a, const PPORcPlan& plan, float* workspace, hipStream_t s);
+// test hook: x [rows][feats] fp32 through the kernel's split-bf16 image store (mode 0 packed, 1 per
+// element) and transposed reads; out [2][feats / 16][max(rows, 32) / 32][64][8] bf16 bit patterns
+hipError_t ppo_image_probe_launch(const float* x, int rows, int feats, int mode, unsigned short* out, hipStream_t s);
 
 // ---- ppo.hip: persistent PPO update
 size_t ppo_lds_bytes(const PPOArgs& a);

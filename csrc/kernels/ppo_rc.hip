@@ -154,9 +154,61 @@ __global__ __launch_bounds__(64 * kPrepWaves) void ppo_rc_prep_kernel(PPOArgs a,
   }
 }
 
+// Test hook (tests/engine/test_ppo_rc_images.py): an fp32 [rows][feats] matrix goes through the
+// update kernel's own image helpers -- stored by 4 row-tile waves as the chain stores a chunk
+// (mode 0: img_store4, a lane's four features of a tile; mode 1: img_store1, the layer-0 lane map
+// of features 4 s + kk), read back as dw_tiles reads its operands -- and every fragment comes out
+// as out[half (hi, lo)][tile][k-step][lane][8] bf16 bit patterns.
+constexpr int kProbeMaxRows = 64, kProbeMaxFeats = 64;
+
+__global__ __launch_bounds__(256) void ppo_image_probe_kernel(const float* x, int rows, int feats, int mode, unsigned short* out) {
+  __shared__ __attribute__((aligned(16))) float lds[kProbeMaxFeats / 16 * 64 * kProbeMaxRows / 4];
+  lf* L = (lf*)lds;
+  const int tid = threadIdx.x, gw = tid >> 6, lane = tid & 63, r16 = lane & 15, kk = lane >> 4;
+  const int rp = rows > 32 ? 64 : 32, T = feats / 16, ksteps = rp / 32;
+  for (int i = tid; i < T * img_strip(rp) / 4; i += 256) L[i] = 0.f;
+  __syncthreads();
+  const int row = 16 * gw + r16;
+  if (row < rows) {
+    if (mode == 0) {
+      const int st = img_unit(row, kk);
+      for (int t = 0; t < T; ++t) {
+        const f4 v = *reinterpret_cast<const f4*>(x + (size_t)row * feats + 16 * t + 4 * kk);
+        bf16x4 hi, lo;
+        split4(v, hi, lo);
+        img_store4(L, 0, rp, t, st, hi, lo);
+      }
+    } else {
+      for (int s = 0; s < feats / 4; ++s) img_store1(L, 0, rp, 4 * s + kk, row, x[(size_t)row * feats + 4 * s + kk]);
+    }
+  }
+  __syncthreads();
+  // (all lanes of all waves: the transposed reads need EXEC all ones)
+  int t0, t1;
+  img_lane_terms(r16, kk, t0, t1);
+  const int n = T * ksteps;
+  for (int i = gw; i < n; i += 4) {  // wave-uniform bounds
+    const int t = i / ksteps, ks = i - t * ksteps;
+    const lch* p = (const lch*)L + t * img_strip(rp) + kImgKStep * ks + t0;
+    const bf16x8 hi = img_read8(p, p + (t1 - t0));
+    const bf16x8 lo = img_read8(p + img_lo(rp), p + img_lo(rp) + (t1 - t0));
+    bf16x8* oh = reinterpret_cast<bf16x8*>(out) + (size_t)i * 64 + lane;  // (whole fragments: 16-byte stores)
+    oh[0] = hi;
+    oh[(size_t)n * 64] = lo;
+  }
+}
+
 }  // namespace rc
 
 using namespace rc;
+
+hipError_t ppo_image_probe_launch(const float* x, int rows, int feats, int mode, unsigned short* out, hipStream_t s) {
+  if (rows <= 0 || rows > kProbeMaxRows || rows % 16 != 0 || feats <= 0 || feats > kProbeMaxFeats || feats % 16 != 0 ||
+      (mode != 0 && mode != 1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ppo_image_probe_kernel, dim3(1), dim3(256), 0, s, x, rows, feats, mode, out);
+  return hipGetLastError();
+}
 
 // The instance table as host rows, in selection order. Every row compiles without scratch
 // (tools/kernel_resources.py, profiles/r4_kernel_resources.md).
@@ -246,8 +298,10 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan) {
   // compiled, so 64-wide nets outside the [64, 64] families take the LDS kernel
   const PPORcRow* row = rc_select(a, KT, cw, ns, env_bf3, false);
   if (row == nullptr) return reject(4);
-  if (row->CWT <= 0) {  // run-time chunk width: at most the rows the net's row-tile waves cover
-    const int cover = 16 * (ns ? row->NW : row->NW / 2);
+  if (row->CWT <= 0) {  // run-time chunk width: at most the rows the net's row-tile waves cover,
+    // and at most 32: the kernel folds the images' 32 padded rows for these rows at compile time
+    int cover = 16 * (ns ? row->NW : row->NW / 2);
+    if (cover > 32) cover = 32;
     if (cw > cover) cw = cover;
     if (a.batch % cw != 0) cw = 16;
   }
@@ -318,15 +372,15 @@ bool ppo_rc_plan(const PPOArgs& a, PPORcPlan& plan) {
   }
   off = pend;
   g.ls_off = take(16);
-  g.zero_off = take(64);
+  take(64);  // (once the zero row of empty dW slots, which now read a real strip; kept so that no plan's LDS moves)
   g.param_lds = off;
-  // activation / dZ images for the dW MFMAs, K-major split-bf16 (ppo_rc_kernel.h img_store):
-  // per 16-padded column cs floats = hi rows [0, rows_pad) + lo rows [rows_pad, 2 rows_pad) in
-  // bf16 (ppo_rc_kernel.h img_lo: 16-byte aligned halves, 68 / 36 dwords per column);
-  // layer-0 input shared by both nets
+  // activation / dZ images for the dW MFMAs, row-major split-bf16 (ppo_rc_kernel.h dw_tiles):
+  // per 16-feature tile one strip of rows_pad rows x 16 features, hi then lo, = 16 rows_pad
+  // floats. A region keeps the (rows_pad + 4) floats per feature of the earlier feature-major
+  // images, so no plan moves; the strips use the first rows_pad of them. Layer-0 input shared by
+  // both nets.
   const int rows_pad = cw > 32 ? cw : 32;
   const int ldr = rows_pad + 4;
-  g.ksteps = rows_pad / 32;
   const int h0 = take(((a.D + 15) & ~15) * ldr);
   const int abase = off;
   int aend = off;

@@ -21,10 +21,10 @@
 //   normalises advantages per minibatch and computes each minibatch's observation
 //   moments; the kernel only Chan-merges those moments (one lane per feature) one
 //   minibatch ahead.
-// * dW (K = rows) needs rows along K, i.e. a transpose: layer inputs and dZ are
-//   stored K-major in LDS once ([column][permuted row], row r at (r & 3) * cw/4 + r / 4,
-//   so the rows 4s + kk that lane group kk feeds to MFMA step s are contiguous and one
-//   ds_read_b128 serves four steps), then every wave computes whole dW tiles over all
+// * dW (K = rows) needs rows along K, i.e. a transpose: layer inputs and dZ are stored once in
+//   LDS as row-major split-bf16 images (a lane's four consecutive features of a row: one 8-byte
+//   store per half) and read back through the transposing ds_read_b64_tr_b16 (see dw_tiles);
+//   every wave computes whole dW tiles over all
 //   rows for the parameter "items" it owns -- all of its weight tiles interleaved, so
 //   their MFMA chains hide each other's latency. The owner keeps that tile's gradient and
 //   Adam moments in registers, so after the grad-norm reduction Adam updates W in
@@ -273,24 +273,83 @@ __device__ __forceinline__ void reduce_slots(const float* slab, float* red, size
 // on v_mfma_f32_16x16x32_bf16 with the split-bf16 ("bf16x3") product: every image value is
 // stored as hi = bf16(v) and lo = bf16(v - hi), and dZ^T H = hi.hi + hi.lo + lo.hi (the lo.lo term
 // is ~2^-16 of the product: near-fp32 accuracy at 3 bf16 MFMAs per 32 rows instead of eight
-// 16x16x4 fp32 ones). Images are K-major (rows contiguous): column c of an image has its hi rows
-// at bf16 index 2 c cs + r and its lo rows at 2 c cs + img_lo(cs) + r (cs floats per column).
-// Lane (r16, kk) reads rows
-// 8 kk .. 8 kk + 7 (+ 32 per K-step) of column r16 of the item's dZ (A, M = out) and H (B,
-// N = in) tiles; the accumulator layout is the fp32 kernel's (C[out 4 kk + j][in r16]), so the
-// exchange and Adam code is unchanged. izo / iho: bf16 offsets of the lane's first element;
-// lo: bf16 offset of the lo half (img_lo).
-// A column of a K-major split-bf16 image is 2 cs bf16 (cs = rows_pad + 4 floats): hi rows at
-// [0, rows_pad), lo rows at [rows_pad, 2 rows_pad), 8 bf16 of padding. The lo half starts at a
-// 16-byte boundary (a ds_read_b128 off its natural alignment stalls ~60 cycles) and the column
-// stride of rows_pad / 4 + 1 (odd) 16-byte slots spreads a read group's 16 columns over the banks.
-__device__ __forceinline__ int img_lo(int cs) { return cs - 4; }
+// 16x16x4 fp32 ones). Lane (r16, kk) feeds rows 8 kk .. 8 kk + 7 (+ 32 per K-step) of feature r16
+// of the item's dZ (A, M = out) and H (B, N = in) tiles; the accumulator layout is the fp32
+// kernel's (C[out 4 kk + j][in r16]), so the exchange and Adam code is unchanged.
+//
+// Image layout: ROW-major, one strip per 16-feature tile. A strip is [rp rows][16 features] bf16
+// of hi values (32-byte rows) followed by the same of lo values (rp = the chunk's rows padded to a
+// multiple of 32), so tile t of the image at float offset off starts at byte 4 off + t img_strip(rp).
+// The chain's lane (row, kk) holds the four consecutive features 4 kk .. 4 kk + 3 of a tile: one
+// 8-byte store per half. The dW lanes need 8 consecutive ROWS of one feature: two transposing
+// reads (ds_read_b64_tr_b16) per half, each a block of 4 rows x 16 features in which lane 4 q + p
+// of a 16-lane group gives the address of row q, features 4 p .. 4 p + 3, and lane i receives
+// feature i with row q in element q. EXEC must be all ones there: every wave runs dw_tiles on
+// every slot, empty ones included.
+// Banks (img_unit): rows 8 .. 11 and 12 .. 15 of every 16 trade places and the four 8-byte units
+// of a row are XORed with (row >> 2) & 3. A store's 16-lane group (16 rows, one unit) then covers
+// all 32 store banks once; a read's 32-lane half (two blocks 8 rows apart, the swap puts them in
+// opposite 128-byte halves of the 256-byte bank row) covers all 64 read banks once.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) bf16x4 lbf4;
+typedef __attribute__((address_space(3))) char lch;
+
+__host__ __device__ __forceinline__ int img_lo(int rp) { return 32 * rp; }     // bytes from a strip's hi to its lo half
+__host__ __device__ __forceinline__ int img_strip(int rp) { return 64 * rp; }  // bytes per tile strip
+// byte offset within a half strip of unit p (features 4 p .. 4 p + 3) of row `row`
+__host__ __device__ __forceinline__ int img_unit(int row, int p) {
+  return 32 * (row ^ ((row >> 1) & 4)) + 8 * (p ^ ((row >> 2) & 3));
+}
+// the dW lane's two block addresses within a strip: rows 8 kk + q and 8 kk + 4 + q, unit p
+// (q = r16 >> 2, p = r16 & 3); a K-step is 32 rows = 1024 bytes further
+__device__ __forceinline__ void img_lane_terms(int r16, int kk, int& t0, int& t1) {
+  t0 = img_unit(8 * kk + (r16 >> 2), r16 & 3);
+  t1 = img_unit(8 * kk + 4 + (r16 >> 2), r16 & 3);
+}
+constexpr int kImgKStep = 32 * 32;
+
+// (no contraction: where v is a product, lo must come from the ROUNDED v -- fma(a, b, -hi) would
+// make hi + lo differ from the fp32 value the rest of the chain uses, and from build to build)
+__device__ __forceinline__ void split4(const f4 v, bf16x4& hi, bf16x4& lo) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bf16 h = (bf16)v[j];
+    hi[j] = h;
+    lo[j] = (bf16)(v[j] - (float)h);
+  }
+}
+__device__ __forceinline__ bf16x8 cat4(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
+
+// a lane's four features of tile t (already split) into the image at float offset off; st: the
+// lane's img_unit(row, kk)
+__device__ __forceinline__ void img_store4(lf* L, int off, int rp, int t, int st, bf16x4 hi, bf16x4 lo) {
+  lch* p = (lch*)L + 4 * off + t * img_strip(rp) + st;
+  *(lbf4*)p = hi;
+  *(lbf4*)(p + img_lo(rp)) = lo;
+}
+// one value (feature f of row `row`) into the image: the layer-0 input, whose lane holds features
+// 4 s + kk and not four consecutive ones
+__device__ __forceinline__ void img_store1(lf* L, int off, int rp, int f, int row, float v) {
+  lch* p = (lch*)L + 4 * off + (f >> 4) * img_strip(rp) + img_unit(row, (f >> 2) & 3) + 2 * (f & 3);
+  const bf16 h = (bf16)v;
+  *(lbf*)p = h;
+  *(lbf*)(p + img_lo(rp)) = (bf16)(v - (float)h);
+}
+// 8 consecutive rows of the lane's feature: the two transposed blocks at a0, a1
+__device__ __forceinline__ bf16x8 img_read8(const lch* a0, const lch* a1) {
+  const bf16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lbf4*)a0);
+  const bf16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lbf4*)a1);
+  return cat4(x, y);
+}
 
 __device__ __forceinline__ f4 mfma_bf16(bf16x8 a, bf16x8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
+// izo / iho: byte offsets of the lane's first block (rows 8 kk + q) of the slot's dZ / H strips;
+// d1: the lane's offset from there to its second block; lo: img_lo
 template <int N>
-__device__ __forceinline__ void dw_tiles(const lf* L, const int* izo, const int* iho, int lo, int ksteps, f4* acc) {
-  const lbf* Lb = (const lbf*)L;
+__device__ __forceinline__ void dw_tiles(const lf* L, const int* izo, const int* iho, int d1, int lo, int ksteps, f4* acc) {
+  const lch* Lb = (const lch*)L;
   // items in groups of GS: independent accumulation chains keep the MFMA pipe busy while only
   // the group's operands (4 x bf16x8 per item) are live (2 per group for the largest slot counts)
   constexpr int GS = N >= 12 ? 2 : 4;
@@ -301,12 +360,12 @@ __device__ __forceinline__ void dw_tiles(const lf* L, const int* izo, const int*
 #pragma unroll
       for (int i = 0; i < GS; ++i) {
         if (i0 + i >= N) continue;
-        const lbf* zp = Lb + izo[i0 + i] + 32 * ks;
-        const lbf* hp = Lb + iho[i0 + i] + 32 * ks;
-        zh[i] = *(const lbf8*)zp;
-        zl[i] = *(const lbf8*)(zp + lo);
-        hh[i] = *(const lbf8*)hp;
-        hl[i] = *(const lbf8*)(hp + lo);
+        const lch* zp = Lb + izo[i0 + i] + kImgKStep * ks;
+        const lch* hp = Lb + iho[i0 + i] + kImgKStep * ks;
+        zh[i] = img_read8(zp, zp + d1);
+        zl[i] = img_read8(zp + lo, zp + lo + d1);
+        hh[i] = img_read8(hp, hp + d1);
+        hl[i] = img_read8(hp + lo, hp + lo + d1);
       }
 #pragma unroll
       for (int i = 0; i < GS; ++i) {
@@ -317,14 +376,6 @@ __device__ __forceinline__ void dw_tiles(const lf* L, const int* izo, const int*
       }
     }
   }
-}
-
-// one value into a split-bf16 K-major image: hi at [col][row], lo one half-column (cs bf16) on
-__device__ __forceinline__ void img_store(lf* L, int off, int cs, int col, int row, float v) {
-  lbf* p = (lbf*)(L + off) + (2 * col * cs + row);
-  const bf16 h = (bf16)v;
-  p[0] = h;
-  p[img_lo(cs)] = (bf16)(v - (float)h);
 }
 
 // ---- split-bf16 forward / input-gradient path (BF3: 32- and 64-wide 3-layer nets, obs dim <= 32)
@@ -594,28 +645,29 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   }
   // dW item operands: this wave's valid weight slots are its first nwi (ids < n_witems);
   // the LDS offsets of a slot's dZ / H columns are a wave-uniform base (the descriptor) plus
-  // ONE lane term shared by every slot (all K-major images have the row stride cw + 4)
+  // ONE lane term shared by every slot (every tile strip has 32-byte rows)
   const int nwi = nwq > w ? min(KW, (nwq - w + kWaves - 1) / kWaves) : 0;
-  // floats per column of the split-bf16 K-major images (ppo_rc_plan: max(cw, 32) + 4) and the
-  // 32-row K-steps of a dW tile: compile-time under a fixed chunk width (offsets fold into the
-  // ds_read immediates)
-  constexpr int kRowsPad = CWT > 32 ? CWT : 32;
-  const int cs = CWT > 0 ? kRowsPad + 4 : rfl(g.ldz[0][0]);
-  const int ksteps = CWT > 0 ? kRowsPad / 32 : rfl(g.ksteps);
-  const int lterm = r16 * 2 * cs + 8 * kk;  // bf16 offset of this lane's first dW operand
+  // rows per strip of the split-bf16 images (ppo_rc_plan: max(cw, 32)) and the 32-row K-steps of
+  // a dW tile, both compile-time (strip and half offsets fold into the ds immediates; as run-time
+  // values the store addresses of every layer and tile are hoisted into registers and the generic
+  // build spills): a run-time chunk width (CWT == 0) is at most 32 rows (ppo_rc_plan)
+  constexpr int rp = CWT > 32 ? CWT : 32;
+  constexpr int ksteps = rp / 32;
+  int lterm, lterm1;  // byte offsets of this lane's two dW operand blocks within a strip
+  img_lane_terms(r16, kk, lterm, lterm1);
   // Per-slot wave-uniform LDS bases: the descriptor and layer tables are kernel-argument arrays,
   // so each dynamically indexed use is a dependent scalar-load chain. The 4-wave builds with at
   // most 8 weight slots resolve them once (HOIST); the 8-wave ones (256 VGPRs, no AGPRs) and the
   // 12 / 14-slot ones (full register file) re-resolve them per use.
-  // slot_dw: the slot's dZ / H operand bases (bf16; + lterm per lane).
+  // slot_dw: the slot's dZ / H strip bases (bytes; + lterm per lane).
   // slot_img (BF3, Adam's image stores): forward image base (+ the lane term of the layer kind:
   // 0 input layer, 1 hidden, 2 head) and its lo-half offset; transposed image base / lo offset.
   constexpr bool HOIST = NW == 4 && KW <= 8;
   auto slot_dw = [&](int it, int& zu, int& hu) {
     const int desc = rfl(g.items[wb + w + it * kWaves]);
     const int iq = desc & 1, il = (desc >> 1) & 3, ta = (desc >> 5) & 15, tb = (desc >> 9) & 15;
-    zu = 2 * rfl(g.z_off[iq][il]) + 16 * ta * 2 * cs;
-    hu = 2 * rfl(g.h_off[iq][il]) + 16 * tb * 2 * cs;
+    zu = 4 * rfl(g.z_off[iq][il]) + ta * img_strip(rp);
+    hu = 4 * rfl(g.h_off[iq][il]) + tb * img_strip(rp);
   };
   auto slot_img = [&](int it, int& kd, int& wf, int& wl, int& wt, int& tl) {
     const int desc = rfl(g.items[wb + w + it * kWaves]);
@@ -701,6 +753,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   }
   Rows<S0M> cur;
   const int row = 16 * gw + r16;
+  const int sterm = img_unit(row, kk);  // this lane's 8-byte unit (features 4 kk .. 4 kk + 3) of a strip
   // chunk unit u = k * nch + ch -> prep slot k * CH + grp * nch + ch
   auto slot_of = [&](int u) -> size_t { return (size_t)(u / nch) * CH + (size_t)grp * nch + (u % nch); };
   if (rows_wave && K > 0) load_rows(g, slot_of(0), row, kk, s0, cur);
@@ -740,7 +793,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       const int h0 = rfl(g.h_off[0][0]);
 #pragma unroll
       for (int s = 0; s < S0M; ++s)
-        if (s < s0) img_store(L, h0, cs, 4 * s + kk, row, xo[s]);
+        if (s < s0) img_store1(L, h0, rp, 4 * s + kk, row, xo[s]);
     }
   };
   // pre_rows: under the exchange (G > 1) or the net split, chunk 0 of minibatch k+1 is
@@ -869,12 +922,14 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
             const int h0 = rfl(g.h_off[0][0]);
 #pragma unroll
             for (int s = 0; s < S0M; ++s)
-              if (s < s0) img_store(L, h0, cs, 4 * s + kk, row, xb[s]);
+              if (s < s0) img_store1(L, h0, rp, 4 * s + kk, row, xb[s]);
           }
         }
         unsigned long long c1 = prof ? clock64() : 0;
         // ---------------- forward (registers)
         f4 hreg[kL - 1][KT];  // outputs of hidden layers (C layout), kept for act'
+        // their split-bf16 halves: the image store's data and (BF3) the next layer's B operand
+        bf16x4 hsp[kL - 1][KT][2];
         f4 head = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int l = 0; l < kL; ++l) {
@@ -898,14 +953,16 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
               if (ks >= ks_l) continue;
-              float v[8];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                if (l == 0) v[j] = j < S0M ? xb[j < S0M ? j : 0] : 0.f;
-                else v[j] = hreg[l > 0 ? l - 1 : 0][2 * ks + (j >> 2)][j & 3];
-              }
               bf16x8 bh, bl;
-              split8(v, bh, bl);
+              if (l == 0) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = j < S0M ? xb[j < S0M ? j : 0] : 0.f;
+                split8(v, bh, bl);
+              } else {  // the halves the image stores took
+                bh = cat4(hsp[l > 0 ? l - 1 : 0][2 * ks][0], hsp[l > 0 ? l - 1 : 0][2 * ks + 1][0]);
+                bl = cat4(hsp[l > 0 ? l - 1 : 0][2 * ks][1], hsp[l > 0 ? l - 1 : 0][2 * ks + 1][1]);
+              }
 #pragma unroll
               for (int t = 0; t < KT; ++t) {
                 if (t >= tout) continue;
@@ -997,10 +1054,8 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
                 hreg[l][t] = v;
                 // input image of layer l + 1 (for its dW)
                 const LG yn = LY(l + 1);
-                img_store(L, yn.h, cs, o0, row, v.x);
-                img_store(L, yn.h, cs, o0 + 1, row, v.y);
-                img_store(L, yn.h, cs, o0 + 2, row, v.z);
-                img_store(L, yn.h, cs, o0 + 3, row, v.w);
+                split4(v, hsp[l][t][0], hsp[l][t][1]);
+                img_store4(L, yn.h, rp, t, sterm, hsp[l][t][0], hsp[l][t][1]);
               }
             } else if (t == 0) {
               head = v;
@@ -1133,14 +1188,16 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
                 for (int j = 0; j < 4; ++j)
                   if (u2 < tin && tt < tout) wt[u2 % KWT][tt % KWT][j] = L[y.w + (16 * tt + 4 * kk + j) * y.ldw + 16 * u2 + r16];
           }
+          // split-bf16 halves of this layer's dZ tiles: the image store's data and (BF3) the B
+          // operand of the W^T product (tiles past tout: zeros)
+          bf16x4 zsp[KT][2];
+#pragma unroll
+          for (int u2 = 0; u2 < KT; ++u2) zsp[u2][0] = zsp[u2][1] = bf16x4{(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
 #pragma unroll
           for (int u2 = 0; u2 < KT; ++u2) {
             if (u2 >= tout) continue;
-            const int zc = 16 * u2 + 4 * kk;
-            img_store(L, y.z, cs, zc, row, dzc[u2].x);
-            img_store(L, y.z, cs, zc + 1, row, dzc[u2].y);
-            img_store(L, y.z, cs, zc + 2, row, dzc[u2].z);
-            img_store(L, y.z, cs, zc + 3, row, dzc[u2].w);
+            split4(dzc[u2], zsp[u2][0], zsp[u2][1]);
+            img_store4(L, y.z, rp, u2, sterm, zsp[u2][0], zsp[u2][1]);
             const float s0v = sum16(dzc[u2].x), s1v = sum16(dzc[u2].y), s2v = sum16(dzc[u2].z), s3v = sum16(dzc[u2].w);
             if (r16 == 0) {
               const f4 sv = {s0v, s1v, s2v, s3v};
@@ -1164,11 +1221,7 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
               if (ks >= ks_l) continue;
-              float v[8];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) v[j] = (2 * ks + (j >> 2)) < tout ? dzc[2 * ks + (j >> 2)][j & 3] : 0.f;
-              bf16x8 bh, bl;
-              split8(v, bh, bl);
+              const bf16x8 bh = cat4(zsp[2 * ks][0], zsp[2 * ks + 1][0]), bl = cat4(zsp[2 * ks][1], zsp[2 * ks + 1][1]);
 #pragma unroll
               for (int u2 = 0; u2 < KT; ++u2) {
                 if (u2 >= tin) continue;
@@ -1243,7 +1296,8 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
         int izo[KW], iho[KW];
 #pragma unroll
         for (int it = 0; it < KW; ++it) {
-          izo[it] = iho[it] = 2 * g.zero_off;  // (bf16 units: the zero row)
+          // (empty slots: tile 0 of the layer-0 input image -- every image holds at least one strip)
+          izo[it] = iho[it] = 4 * rfl(g.h_off[0][0]) + lterm;
           if (it < nwi) {
             int zu, hu;
             if constexpr (HOIST) {
@@ -1258,9 +1312,10 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
         }
         // the chunk's dZ^T H continues each slot's MFMA chain from its running gradient
         // (padding entries are exactly 0: zeroed images)
-        // (empty slots read the zero row: their MFMAs add zeros to gradients nobody reads,
-        // so every wave runs the same straight-line body)
-        dw_tiles<KW>(L, izo, iho, img_lo(cs), ksteps, gg);
+        // (empty slots read finite values of a real strip: their MFMAs run on gradients nobody
+        // reads, so every wave runs the same straight-line body with all lanes on -- the
+        // transposed reads need that)
+        dw_tiles<KW>(L, izo, iho, lterm1 - lterm, img_lo(rp), ksteps, gg);
       }
 #pragma unroll
       for (int ib = 0; ib < KB; ++ib) {
