@@ -16,7 +16,7 @@
 // [64, 64] net up to an obs dim bound), GENERIC (run-time shape) -- and IA_RC_TABLE orders the
 // tiers: an exact build wins over the family that also covers its shape, the obs dim <= 16
 // families over the <= 32 ones, and the generic builds take what is left.
-// Scratch budget of every instance: profiles/ppo_chain_trim.md (all 0; before the lean rows:
+// Scratch budget of every instance: profiles/ppo_barrier_path.md (all 0; before the lean rows:
 // profiles/r4_kernel_resources.md).
 #pragma once
 

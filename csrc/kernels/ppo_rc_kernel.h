@@ -20,7 +20,7 @@
 //   gathers every minibatch of every epoch in parallel (perm is known up front),
 //   normalises advantages per minibatch and computes each minibatch's observation
 //   moments; the kernel only Chan-merges those moments (one lane per feature) one
-//   minibatch ahead.
+//   minibatch ahead (net-split builds: two, in the Adam window of the wave with the fewest items).
 // * dW (K = rows) needs rows along K, i.e. a transpose: layer inputs and dZ are stored once in
 //   LDS as row-major split-bf16 images (a lane's four consecutive features of a row: one 8-byte
 //   store per half) and read back through the transposing ds_read_b64_tr_b16 (see dw_tiles);
@@ -532,6 +532,17 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   constexpr int S0M = S0T > 0 ? S0T : (S0T < 0 ? -S0T : 16);
   const int s0 = S0T > 0 ? S0T : (D + 3) / 4;
   constexpr bool BF3 = rc_is_bf3(KT, S0T, NLT, HWT, CWT, NW);
+  // kOffPath: the net-split builds (4 waves, one vector slot per wave) keep one-lane serial work
+  // off the barrier-to-barrier path: the entropy sum is read in one batch behind B1 by the last
+  // wave (ent_wave), the normaliser's Chan merge runs two minibatches ahead in the Adam window
+  // (norm_merge), the bias / log-std partials and (kNormBatch: exact input width) norm_rows' mean /
+  // rstd pairs are read in one batch each. Same values, same order of every sum.
+  // The other builds keep the earlier order: the 8-wave ones have no registers for the batches
+  // (cheetah32_cw64 would take 20 B of scratch), and in the builds with two vector slots per wave
+  // (both nets per workgroup, generic) the compiler packs the two slots' Adam arithmetic into
+  // v_pk_fma_f32 differently once the merge follows it, which moves last bits of the moments.
+  constexpr bool kOffPath = KB == 1 && NW == 4;
+  constexpr bool kNormBatch = kOffPath && S0T > 0 && KW <= 8;
   const bool gauss = DT >= 0 ? DT == 0 : !a.discrete;
   const bool has_ls = gauss && a.log_std_off >= 0;
   float am[4];  // action-slot masks of this lane group (Gaussian head)
@@ -567,8 +578,12 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
     }
   }
   if (tid < 16) L[g.ls_off + tid] = (has_ls && tid < A && !(ns && q != 0)) ? a.params[a.log_std_off + tid] : 0.f;
+  // no normaliser: the exact-width builds read the normaliser image unconditionally (norm_rows),
+  // so both halves hold mean 0 (zeroed above) and rstd 1 -- (x - 0) * 1, as without the image
+  if constexpr (kNormBatch)
+    if (!a.has_norm && tid < 64) L[g.nm_off + 64 + tid] = L[g.nm_off + 128 + 64 + tid] = 1.f;
   // normaliser running state (double-buffered per-minibatch mean / rstd)
-  // (owned by wave 7, one lane per feature)
+  // (owned by the last wave, one lane per feature)
   const int nc = tid - (kThreads - 64);
   const bool norm_lane = a.has_norm && nc >= 0 && nc < D;
   float run_m = 0.f, run_v = 1.f, run_c = 0.f;
@@ -633,16 +648,21 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   float step = a.adam_step[0];
   float b1t = powf(a.beta1, step), b2t = powf(a.beta2, step);
   const int hid_act = ACTT >= 0 ? ACTT : a.hidden_act;
-  // first minibatch norm stats
-  if (norm_lane && K > 0) {
-    const float m = g.mom[nc], v = g.mom[64 + nc], n = (float)Bg;
-    const float tot = run_c + n, delta = m - run_m;
+  // Chan merge of minibatch m's observation moments into the running normaliser state and into
+  // half (m & 1) * 128 of the double-buffered normaliser image (one lane per feature, last wave).
+  // kOffPath: the first two minibatches are merged here, minibatch k + 2 in minibatch k's Adam
+  // window; otherwise the first one here and minibatch k + 1 behind minibatch k's B1.
+  auto norm_merge = [&](float mom_m, float mom_v, int half) {
+    const float n = (float)Bg;
+    const float tot = run_c + n, delta = mom_m - run_m;
     run_m += delta * n / tot;
-    run_v = (run_v * run_c + v * n + delta * delta * run_c * n / tot) / tot;
+    run_v = (run_v * run_c + mom_v * n + delta * delta * run_c * n / tot) / tot;
     run_c = tot;
-    L[g.nm_off + nc] = run_m;
-    L[g.nm_off + 64 + nc] = rsqrtf(run_v + a.norm_eps);
-  }
+    L[g.nm_off + half + nc] = run_m;
+    L[g.nm_off + half + 64 + nc] = rsqrtf(run_v + a.norm_eps);
+  };
+  if (norm_lane && K > 0) norm_merge(g.mom[nc], g.mom[64 + nc], 0);
+  if (kOffPath && norm_lane && K > 1) norm_merge(g.mom[128 + nc], g.mom[128 + 64 + nc], 128);
   // dW item operands: this wave's valid weight slots are its first nwi (ids < n_witems);
   // the LDS offsets of a slot's dZ / H columns are a wave-uniform base (the descriptor) plus
   // ONE lane term shared by every slot (every tile strip has 32-byte rows)
@@ -746,10 +766,11 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
     b_okf[ib] = ok ? 1.f : 0.f;
     if (ok) b_addr[ib] = kind == 1 ? y.b + lane : g.ls_off + lane;
   }
-  float pre_m = 0.f, pre_v = 0.f;  // moments of the next minibatch to merge
-  if (norm_lane && K > 1) {
-    pre_m = g.mom[128 + nc];
-    pre_v = g.mom[128 + 64 + nc];
+  float pre_m = 0.f, pre_v = 0.f;  // moments of the next minibatch to merge (loaded a minibatch ahead)
+  constexpr int kAhead = kOffPath ? 2 : 1;  // minibatches the merge runs ahead of the chunks
+  if (norm_lane && K > kAhead) {
+    pre_m = g.mom[kAhead * 128 + nc];
+    pre_v = g.mom[kAhead * 128 + 64 + nc];
   }
   Rows<S0M> cur;
   const int row = 16 * gw + r16;
@@ -780,11 +801,18 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
     float nmv[S0M], nrv[S0M];
 #pragma unroll
     for (int s = 0; s < S0M; ++s) {
-      nmv[s] = 0.f;
-      nrv[s] = 1.f;
-      if (s < s0 && a.has_norm) {
+      if constexpr (kNormBatch) {
+        // exact input width: every mean / rstd pair is read, in one batch, with no branch between
+        // the reads (without a normaliser the image holds mean 0 / rstd 1 from the prologue)
         nmv[s] = L[g.nm_off + nbuf + 4 * s + kk];
         nrv[s] = L[g.nm_off + nbuf + 64 + 4 * s + kk];
+      } else {
+        nmv[s] = 0.f;
+        nrv[s] = 1.f;
+        if (s < s0 && a.has_norm) {
+          nmv[s] = L[g.nm_off + nbuf + 4 * s + kk];
+          nrv[s] = L[g.nm_off + nbuf + 64 + 4 * s + kk];
+        }
       }
     }
 #pragma unroll
@@ -799,7 +827,8 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   // pre_rows: under the exchange (G > 1) or the net split, chunk 0 of minibatch k+1 is
   // normalised while this workgroup waits for its partners (arrival / |g|^2 hand-off): its
   // rows are in cur since the last chunk, its normaliser buffer was merged after this
-  // minibatch's B1, and every dW read of the layer-0 image is behind the barrier before it
+  // minibatch's B1 (kOffPath: in the previous minibatch's Adam window), and every dW read of the
+  // layer-0 image is behind the barrier before it
   // (not the 12 / 14-slot builds: their register file is full; not with the G > 16 partial
   // stash, which borrows the activation images -- the layer-0 input image included -- during
   // the exchange)
@@ -842,6 +871,16 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
   f4 pbs[PL][PT];
   f4 pls = {0.f, 0.f, 0.f, 0.f};
 
+  // Gaussian entropy term (kOffPath): the sum of log_std, taken by the last wave (it owns the
+  // fewest items) right after B1 from four 16-byte broadcast reads that run under its dW items -- log_std is
+  // rewritten only by Adam, behind B2. The 16-entry vector is zero past A (and all zero without a
+  // log-std), and the sum runs in ascending j from +0, so the trailing + 0.f terms change no bit
+  // (the running sum is never -0). Lane 0 of that wave keeps st_ent: the stats epilogue adds one
+  // non-zero term and zeros, in any wave order the same value.
+  // (net split: the actor workgroup; its critic twin holds no log_std and adds nothing)
+  const bool ent_wave = kOffPath && gauss && grp == 0 && (!ns || q == 0) && w == kWaves - 1;
+  float ent_sl = 0.f;
+
   for (int k = 0; k < K; ++k) {
     unsigned long long t0 = prof ? clock64() : 0;
     const int nb = (k & 1) * 128;  // norm buffer of minibatch k
@@ -882,14 +921,16 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       const int u = k * nch + ch;
       Rows<S0M> nxt;
       if (rows_wave && u + 1 < K * nch) load_rows(g, slot_of(u + 1), row, kk, s0, nxt);
-      // moments of minibatch k+1 (prefetched one minibatch earlier) -> registers; issue k+2
+      // (!kOffPath) moments of minibatch k+1 (prefetched one minibatch earlier) -> registers; issue k+2
       float mom_m = 0.f, mom_v = 0.f;
-      if (ch == 0 && norm_lane) {
-        mom_m = pre_m;
-        mom_v = pre_v;
-        if (k + 2 < K) {
-          pre_m = g.mom[(size_t)(k + 2) * 128 + nc];
-          pre_v = g.mom[(size_t)(k + 2) * 128 + 64 + nc];
+      if constexpr (!kOffPath) {
+        if (ch == 0 && norm_lane) {
+          mom_m = pre_m;
+          mom_v = pre_v;
+          if (k + 2 < K) {
+            pre_m = g.mom[(size_t)(k + 2) * 128 + nc];
+            pre_v = g.mom[(size_t)(k + 2) * 128 + 64 + nc];
+          }
         }
       }
       unsigned long long c0 = prof ? clock64() : 0;
@@ -1279,16 +1320,20 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       const unsigned long long cb0 = prof ? clock64() : 0;
       __syncthreads();  // B1: H / dZ images, bias and log-std partials of this chunk complete
       const unsigned long long cb1 = prof ? clock64() : 0;
-      // Chan merge for minibatch k+1 (one lane per feature, wave 7), off the chain's critical
-      // path; minibatch k reads the other half of the double-buffered normaliser image
-      if (ch == 0 && norm_lane && k + 1 < K) {
-        const float n = (float)Bg;
-        const float tot = run_c + n, delta = mom_m - run_m;
-        run_m += delta * n / tot;
-        run_v = (run_v * run_c + mom_v * n + delta * delta * run_c * n / tot) / tot;
-        run_c = tot;
-        L[g.nm_off + (128 - nb) + nc] = run_m;
-        L[g.nm_off + (128 - nb) + 64 + nc] = rsqrtf(run_v + a.norm_eps);
+      // Chan merge for minibatch k+1, off the chain's critical path; minibatch k reads the other
+      // half of the double-buffered normaliser image (kOffPath: in the Adam window, below B2)
+      if constexpr (!kOffPath)
+        if (ch == 0 && norm_lane && k + 1 < K) norm_merge(mom_m, mom_v, 128 - nb);
+      if (ent_wave) {  // sum of log_std for the entropy term: reads in flight under the dW items
+        f4 e4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) e4[i] = *(const lf4*)(L + g.ls_off + 4 * i);
+        float sl = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sl += e4[i][j];
+        ent_sl = sl;
       }
 
       // ---------------- dW / db / dlog_std partials of this chunk for the owned items
@@ -1323,7 +1368,16 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
         {  // bias (row-tile partials of dZ) / log_std (partials of the Gaussian term)
           const int stride = bkind[ib] == 1 ? 64 : 16;
           float gval = 0.f;  // (lanes past the vector read finite neighbours, masked by b_okf)
-          for (int r = 0; r < RT; ++r) gval += L[b_off[ib] + r * stride + lane];
+          if constexpr (kOffPath && CWT > 0) {  // compile-time row tiles: every read in flight, then the same sum
+            constexpr int RTC = CWT / 16;
+            float pv[RTC];
+#pragma unroll
+            for (int r = 0; r < RTC; ++r) pv[r] = L[b_off[ib] + r * stride + lane];
+#pragma unroll
+            for (int r = 0; r < RTC; ++r) gval += pv[r];
+          } else {
+            for (int r = 0; r < RT; ++r) gval += L[b_off[ib] + r * stride + lane];
+          }
           bg[ib] += gval * b_okf[ib];
         }
       }
@@ -1528,7 +1582,12 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
     ss = wave_sum(ss);
     if (lane == 0) L[g.red_off + w] = ss;
     // Gaussian entropy loss uses log_std before this minibatch's update
-    if (gauss && tid == 0 && grp == 0 && q == 0) {
+    if constexpr (kOffPath) {  // (ent_sl: summed behind B1 by the last wave, see ent_wave)
+      if (ent_wave && lane == 0) {
+        const float sl = ent_sl;
+        st_ent += -(sl + A * (0.5f + c_half_log2pi));
+      }
+    } else if (gauss && tid == 0 && grp == 0 && q == 0) {
       float sl = 0.f;
       for (int j = 0; j < A; ++j) sl += has_ls ? L[g.ls_off + j] : 0.f;
       st_ent += -(sl + A * (0.5f + c_half_log2pi));
@@ -1641,6 +1700,23 @@ __global__ __launch_bounds__(64 * NW) void ppo_rc_kernel(PPOArgs a, PPORcGeo g) 
       bv[ib] = b2 * bv[ib] + (1.f - b2) * gval * gval;
       const float denom = __builtin_amdgcn_sqrtf(bv[ib]) * inv_bc2s + eps;
       L[b_addr[ib]] = bval[ib] - step_size * bm[ib] * __builtin_amdgcn_rcpf(denom);
+    }
+    // Chan merge for minibatch k+2, behind the last wave's own Adam items (it owns the fewest and
+    // waits at B3 anyway) instead of on the dW path between B1 and B2. Its half of the normaliser
+    // image is minibatch k's (nb): last read by this minibatch's chunks, all behind B2, and next by
+    // pre_rows(k+1) or minibatch k+2's chunks, behind B3; pre_rows(k), which may run in this
+    // window, reads the other half. The moments came in a minibatch ago; k+3's are issued now.
+    // (the wave test is uniform, so that the other waves take a scalar branch over the merge's ~60
+    // instructions and three divides; with the per-lane test alone the B2-to-B3 window measured
+    // 0.3 K cycles longer, profiles/ppo_barrier_path.md)
+    if (kOffPath && w == kWaves - 1 && k + 2 < K) {
+      if (norm_lane) {
+        norm_merge(pre_m, pre_v, nb);
+        if (k + 3 < K) {
+          pre_m = g.mom[(size_t)(k + 3) * 128 + nc];
+          pre_v = g.mom[(size_t)(k + 3) * 128 + 64 + nc];
+        }
+      }
     }
     if (kProfAdam && prof && tid == 0) {
       const unsigned long long a1 = clock64();
