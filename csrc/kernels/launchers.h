@@ -518,4 +518,24 @@ hipError_t oneshot_clear_error(void* local);
 long long oneshot_ticks_per_second();
 hipError_t oneshot_allreduce(const OneShotArgs& a, hipStream_t s);
 
+// ---- comm.hip: two-phase (reduce-scatter + all-gather) all-reduce for MB-sized buckets; IPC
+// open / close / free, the error word and the tick rate are the one-shot helpers above
+constexpr int kTwoPhaseMaxBlocks = 128;  // 8 ranks on one card: 8 x 128 x 256 threads <= half its residency
+struct TwoPhaseArgs {
+  char* base[kOneShotMaxRanks];  // every rank's region as mapped in this process (base[rank] local)
+  const void* in;                // 16-B aligned, float (f64 == 0) or double elements
+  void* out;                     // 16-B aligned, may alias in
+  int n, rank, world;            // n: elements
+  int f64;
+  double scale;                  // applied while staging (1/world -> mean)
+  size_t slot_bytes;             // staging area = result area = slot_bytes
+  long long timeout_ticks;       // per wait; past it the block writes NaN over its slice + error word
+};
+size_t twophase_region_bytes(size_t slot_bytes);
+int twophase_blocks(int n, size_t slot_bytes, int elem_bytes = 4);
+// shard r of the block slice [v0, v1) (16-byte vectors) cut into `world` contiguous shards
+void twophase_shard(int v0, int v1, int world, int r, int* lo, int* hi);
+hipError_t oneshot_alloc_region(size_t region_bytes, void** ptr, void* handle);  // oneshot_alloc by region size
+hipError_t twophase_allreduce(const TwoPhaseArgs& a, hipStream_t s);
+
 }  // namespace ia

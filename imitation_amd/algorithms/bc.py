@@ -525,6 +525,7 @@ class _DeviceEpochRunner:
             from imitation_amd.utils.streams import shared_stream
 
             self._dp_side = shared_stream(self.agg.device, "bc_dp_reduce")
+            self._large = _DeviceEpochRunner.dp_large(opt, self._comm)
         kmax = max(1, int(os.environ.get("IMITATION_AMD_BC_GRAPH_K", self.K)))
         # graph sizes: the largest, then powers of two below it. A run of n steps replays the
         # largest as often as it fits and each smaller one at most once, so the remainder is
@@ -546,7 +547,8 @@ class _DeviceEpochRunner:
         """Under data parallelism, the one-shot communicator (``parallel/oneshot.py``: one kernel,
         capture-safe) when it can reduce the optimizer's single flat gradient bucket in chunks of
         its staging size; None otherwise (then the per-minibatch ``_DPFusedStep`` runs). Every rank
-        reaches this at the same point (the communicator's creation is collective)."""
+        reaches this at the same point (the communicator's creation is collective, and so is that
+        of the two-phase communicator asked for here when the bucket exceeds the one-shot slot)."""
         if pdist.world_size() <= 1:
             return None
         from imitation_amd.parallel import oneshot
@@ -555,12 +557,28 @@ class _DeviceEpochRunner:
         if comm is None or not (hasattr(optimizer, "graph_epoch_step_ok") and optimizer.graph_epoch_step_ok()):
             return None
         flat = optimizer.flat_grads[0]
-        return comm if comm.fits(flat[: min(flat.numel(), comm.stage_bytes // 4 // 4 * 4)]) else None
+        if not comm.fits(flat[: min(flat.numel(), comm.stage_bytes // 4 // 4 * 4)]):
+            return None
+        _DeviceEpochRunner.dp_large(optimizer, comm)  # (collective on its first call)
+        return comm
+
+    @staticmethod
+    def dp_large(optimizer, comm):
+        """The two-phase communicator (``oneshot.get_large``: reduce-scatter + all-gather in one
+        capturable kernel) sized for the flat gradient bucket, when that bucket exceeds the
+        one-shot slot; None otherwise, or when it is unavailable (everything then goes through
+        the one-shot kernel in chunks)."""
+        from imitation_amd.parallel import oneshot
+
+        nbytes = optimizer.flat_grads[0].numel() * 4
+        return oneshot.get_large(nbytes) if nbytes > comm.stage_bytes else None
 
     def _dp_ranges(self):
         """(FC range, other ranges) of the flat gradient bucket, each split into one-shot chunks
         (<= staging size, 16-B multiples): the FC layer's gradients (6.4 of NatureCNN's 6.7 MB) are
-        final right after ``fc_backward``, the conv / head ones only after the conv backward."""
+        final right after ``fc_backward``, the conv / head ones only after the conv backward. With
+        the two-phase communicator present, a range larger than the one-shot slot (that it can
+        hold) is ONE part, reduced by it in one launch."""
         r = getattr(self, "_ranges", None)
         if r is not None:
             return r
@@ -570,7 +588,11 @@ class _DeviceEpochRunner:
         lo = (w.data_ptr() - flat.data_ptr()) // 4
         hi = lo + w.numel()
 
+        large = getattr(self, "_large", None)
+
         def chunks(a, b):
+            if large is not None and step < b - a and (b - a) * 4 <= large.stage_bytes:
+                return [flat[a:b]]
             return [flat[i : min(b, i + step)] for i in range(a, b, step)]
 
         if lo % 4 or hi % 4:
@@ -584,11 +606,12 @@ class _DeviceEpochRunner:
         return r
 
     def _dp_allreduce(self, parts) -> None:
-        """Mean over ranks, inside the captured step: one-shot kernels over ``parts`` (rank-order sum
-        of grad / world per element: bitwise the eager ``FlatGradBucket.allreduce``, whatever the
-        chunking)."""
+        """Mean over ranks, inside the captured step: one-shot kernels over ``parts``, the two-phase
+        kernel for a part larger than the one-shot slot (both: rank-order sum of grad / world per
+        element, bitwise the eager ``FlatGradBucket.allreduce``, whatever the chunking)."""
         for t in parts:
-            self._comm.allreduce_(t, 1.0 / self._world)
+            comm = self._comm if t.numel() * 4 <= self._comm.stage_bytes else self._large
+            comm.allreduce_(t, 1.0 / self._world)
 
     def _one_step(self):
         C = self._f.C

@@ -200,9 +200,9 @@ def check_comm(where: str = "", blocking: bool = False) -> None:
         return
     from imitation_amd.parallel import oneshot
 
-    c = oneshot._COMM
-    if c is not None:
-        c.check(where, blocking=blocking)
+    for c in (oneshot._COMM, oneshot._LARGE):  # the small-bucket and the two-phase communicator
+        if c is not None:
+            c.check(where, blocking=blocking)
 
 
 def allreduce_scalars(values: Sequence[float], op: str = "sum", device=None) -> List[float]:

@@ -1,4 +1,5 @@
-"""One-shot all-reduce for small data-parallel buckets (kernel: ``csrc/kernels/comm.hip``).
+"""IPC all-reduces of the data-parallel runtime (kernels: ``csrc/kernels/comm.hip``):
+the one-shot kernel for small buckets and the two-phase kernel for the one MB-sized bucket.
 
 The DP runtime reduces KB-sized buckets several times per round (discriminator gradients,
 normaliser moment sums; reference hook points ``algorithms/adversarial/common.py:371-372``,
@@ -16,7 +17,16 @@ Selection (``IMITATION_AMD_ONESHOT``):
 * ``0`` -- off (every collective goes to torch.distributed).
 
 Buckets larger than ``IMITATION_AMD_ONESHOT_MAX_BYTES`` (default 1 MiB) keep RCCL, whose
-pipelined ring wins once the message is bandwidth bound.
+pipelined ring wins once the message is bandwidth bound -- with one exception: the flat
+gradient bucket of graph-resident data-parallel BC (``algorithms/bc.py``), whose reduction has
+to be a capturable kernel. Its ranges above the one-shot slot go through :class:`TwoPhaseComm`
+(:func:`get_large`): a reduce-scatter followed by an all-gather in ONE kernel over a slot of the
+bucket's size. Every rank stages its bucket, sums its own 1/W shard of every block slice over
+the ranks in rank order, and copies the other shards from their owners: 2(W-1)/W x bucket
+bytes per rank instead of the one-shot kernel's (W-1) x bucket, two hand-shakes per call
+whatever the size, the same bounded waits / NaN poisoning / error word, and per element the
+same ``x_r * scale`` summed in rank order -- bitwise the one-shot result. It follows the same
+``IMITATION_AMD_ONESHOT`` selection and has no switch of its own.
 """
 
 from __future__ import annotations
@@ -29,14 +39,21 @@ import torch.distributed as tdist
 
 _COMM: Optional["OneShotComm"] = None
 _TRIED = False
+_LARGE: Optional["TwoPhaseComm"] = None
+_LARGE_TRIED = False
+
+LARGE_MAX_BYTES = 64 << 20  # largest two-phase slot (the region holds a staging and a result area of it)
 
 
 class OneShotComm:
     """IPC-mapped staging regions of all ranks + the one-shot all-reduce launch."""
 
+    KIND = "one-shot"
+    MAX_BLOCKS = 64  # kOneShotMaxBlocks
+
     def __init__(self, native, rank: int, world: int, device: torch.device, stage_bytes: int, timeout_s: float):
         if world > 8:
-            raise ValueError("one-shot all-reduce supports up to 8 ranks")
+            raise ValueError(f"{self.KIND} all-reduce supports up to 8 ranks")
         self._C = native
         self.rank, self.world, self.device = rank, world, device
         self.stage_bytes = int(stage_bytes)
@@ -47,14 +64,14 @@ class OneShotComm:
         handle = None
         try:
             with torch.cuda.device(device):
-                self.local, handle = native.oneshot_alloc(self.stage_bytes)
+                self.local, handle = self._alloc()
         except Exception:
             handle = None
         handles = [None] * world
         tdist.all_gather_object(handles, handle)  # every rank learns whether every rank allocated
         if any(h is None for h in handles):
             self.close()
-            raise RuntimeError("one-shot all-reduce: staging allocation failed on some rank")
+            raise RuntimeError(f"{self.KIND} all-reduce: staging allocation failed on some rank")
         opened = True
         try:
             with torch.cuda.device(device):
@@ -69,8 +86,15 @@ class OneShotComm:
             opened = False
         if not _agree(opened, device):
             self.close()
-            raise RuntimeError("one-shot all-reduce: IPC mapping failed on some rank")
+            raise RuntimeError(f"{self.KIND} all-reduce: IPC mapping failed on some rank")
         self.calls = 0
+
+    # the two hooks a communicator over another kernel of comm.hip replaces (TwoPhaseComm)
+    def _alloc(self):
+        return self._C.oneshot_alloc(self.stage_bytes)
+
+    def _launch(self, flat: torch.Tensor, scale: float) -> None:
+        self._C.oneshot_allreduce(self.bases, self.rank, flat, flat, scale, self.stage_bytes, self.timeout_s)
 
     def fits(self, t: torch.Tensor) -> bool:
         return (t.is_cuda and t.device == self.device and t.dtype in (torch.float32, torch.float64) and t.is_contiguous()
@@ -79,7 +103,7 @@ class OneShotComm:
     def allreduce_(self, t: torch.Tensor, scale: float = 1.0) -> None:
         """``t <- sum_r scale * t_r`` in place (rank-order sum, identical on all ranks)."""
         flat = t.view(-1)
-        self._C.oneshot_allreduce(self.bases, self.rank, flat, flat, float(scale), self.stage_bytes, self.timeout_s)
+        self._launch(flat, float(scale))
         self.calls += 1
 
     def error(self) -> int:
@@ -113,12 +137,12 @@ class OneShotComm:
                     self._err_ev.record()
         if err:
             self.clear_error()
-            raise RuntimeError(f"one-shot all-reduce timed out waiting for a peer{(' (' + where + ')') if where else ''}: "
+            raise RuntimeError(f"{self.KIND} all-reduce timed out waiting for a peer{(' (' + where + ')') if where else ''}: "
                                "its output was poisoned with NaN; aborting the run")
 
     def block_floats(self) -> int:
         """Floats per block slice (a bucket of n floats runs ceil(n / block_floats) blocks)."""
-        return 4 * max(256, -(-(self.stage_bytes // 16) // 64))
+        return 4 * max(256, -(-(self.stage_bytes // 16) // self.MAX_BLOCKS))
 
     def blocks(self, n: int) -> int:
         return int(self._C.oneshot_blocks(int(n), self.stage_bytes))
@@ -147,7 +171,7 @@ class OneShotComm:
         # or pair wrongly. (One-shot calls only wait on peers, boundedly.)
         w = self.world
         try:
-            for n in (1, 5, 1027, min(self.stage_bytes // 4, 16384 + 3)):
+            for n in self._closed_form_sizes():
                 for rep in range(2):
                     try:
                         x = torch.arange(n, dtype=torch.float32, device=self.device) * (self.rank + 1) + rep
@@ -157,7 +181,7 @@ class OneShotComm:
                             reasons.append(f"closed-form mismatch at n={n}")
                     except Exception as e:  # noqa: BLE001 -- any failure disables the path
                         reasons.append(f"closed form n={n} raised {e!r}")
-            n = min(self.stage_bytes // 4, 4099)
+            n = self._cross_check_size()
             g = torch.Generator().manual_seed(1234 + self.rank)
             exact = (torch.randint(-512, 512, (n,), generator=g).float() + 0.5 * (self.rank % 2)).to(self.device)
             fuzzy = torch.randn(n, generator=g).to(self.device)
@@ -167,7 +191,7 @@ class OneShotComm:
                     mine = t.clone()
                     self.allreduce_(mine)
                 except Exception as e:  # noqa: BLE001
-                    reasons.append(f"{name} one-shot call raised {e!r}")
+                    reasons.append(f"{name} {self.KIND} call raised {e!r}")
                     mine = None
                 ref = self._reference_allreduce(t)  # (issued on every rank)
                 if mine is None:
@@ -190,6 +214,12 @@ class OneShotComm:
             reasons.append("failed on another rank")
         return ok, "; ".join(reasons)
 
+    def _closed_form_sizes(self):
+        return (1, 5, 1027, min(self.stage_bytes // 4, 16384 + 3))
+
+    def _cross_check_size(self) -> int:
+        return min(self.stage_bytes // 4, 4099)
+
     def _reference_allreduce(self, t: torch.Tensor) -> torch.Tensor:
         ref = t.clone() if tdist.get_backend() == "nccl" else t.detach().cpu().clone()
         tdist.all_reduce(ref)
@@ -204,6 +234,41 @@ class OneShotComm:
         if self.local is not None:
             self._C.oneshot_free(self.local)
             self.local = None
+
+
+def twophase_shard(v0: int, v1: int, world: int, r: int):
+    """Shard ``r`` of the block slice ``[v0, v1)`` of 16-byte vectors: ``(lo, hi)``, the mirror of
+    ``twophase_shard`` in ``comm.hip`` (contiguous, in rank order, empty where the slice has
+    fewer vectors than ranks)."""
+    n = v1 - v0
+    return v0 + n * r // world, v0 + n * (r + 1) // world
+
+
+class TwoPhaseComm(OneShotComm):
+    """The same IPC set-up over a two-phase region (flags for both phases, a staging and a result
+    area of ``stage_bytes`` each) + the reduce-scatter / all-gather launch, for MB-sized buckets.
+    Same public surface as :class:`OneShotComm`; ``stage_bytes`` is the slot (largest bucket)."""
+
+    KIND = "two-phase"
+    MAX_BLOCKS = 128  # kTwoPhaseMaxBlocks
+
+    def _alloc(self):
+        return self._C.twophase_alloc(self.stage_bytes)
+
+    def _launch(self, flat: torch.Tensor, scale: float) -> None:
+        self._C.twophase_allreduce(self.bases, self.rank, flat, flat, scale, self.stage_bytes, self.timeout_s)
+
+    def blocks(self, n: int) -> int:
+        return int(self._C.twophase_blocks(int(n), self.stage_bytes))
+
+    # the self-test of OneShotComm at sizes that reach this kernel's edges: fewer vectors than
+    # ranks (empty shards) with a scalar tail, one vector in a second block, an uneven cut
+    def _closed_form_sizes(self):
+        per, cap = self.block_floats(), self.stage_bytes // 4
+        return tuple(min(cap, n) for n in (1, 4 * (self.world - 1) + 1, per + 4, 3 * per + 4 * self.world + 7))
+
+    def _cross_check_size(self) -> int:
+        return min(self.stage_bytes // 4, self.block_floats() + 4 * (self.world - 1) + 3)
 
 
 def _agree(ok: bool, device: torch.device) -> bool:
@@ -268,6 +333,39 @@ def get() -> Optional[OneShotComm]:
     return _COMM
 
 
+def get_large(nbytes: int) -> Optional[TwoPhaseComm]:
+    """The process-wide two-phase communicator for a bucket of ``nbytes``; None whenever
+    :func:`get` returns None, or when ``nbytes`` does not fit its slot. The first call creates
+    and self-tests it (collective: every rank calls this at the same point with the same
+    ``nbytes``), with a slot of ``nbytes`` rounded up to 16 B x the block count (every block
+    slice whole) and capped at ``LARGE_MAX_BYTES``. It is never re-created: captured graphs hold
+    its addresses. Same selection as the one-shot path (``IMITATION_AMD_ONESHOT``)."""
+    global _LARGE, _LARGE_TRIED
+    small = get()
+    if small is None:
+        return None
+    if not _LARGE_TRIED:
+        _LARGE_TRIED = True
+        mode = _mode()
+        unit = 16 * TwoPhaseComm.MAX_BLOCKS
+        slot = min(LARGE_MAX_BYTES, max(unit, -(-int(nbytes) // unit) * unit))
+        comm = None
+        try:
+            comm = TwoPhaseComm(small._C, small.rank, small.world, small.device, slot, small.timeout_s)
+        except Exception as e:  # keep the chunked one-shot / torch.distributed routes
+            if mode not in ("auto",):
+                raise
+            import logging
+
+            logging.getLogger(__name__).warning("two-phase all-reduce unavailable: %r", e)
+        if comm is not None:
+            _LARGE = adopt(comm, mode)
+            if _LARGE is not None:
+                _LARGE.calls = 0  # count the callers' reductions, not the self-test's
+    c = _LARGE
+    return c if c is not None and int(nbytes) <= c.stage_bytes else None
+
+
 DISABLED_REASON: Optional[str] = None
 
 
@@ -294,12 +392,13 @@ def adopt(comm, mode: str = "auto"):
 
 
 def reset() -> None:
-    """Drop the communicator (process-group teardown)."""
-    global _COMM, _TRIED
-    if _COMM is not None:
-        try:
-            _COMM.close()
-        except Exception:
-            pass
-    _COMM = None
-    _TRIED = False
+    """Drop the communicators (process-group teardown)."""
+    global _COMM, _TRIED, _LARGE, _LARGE_TRIED
+    for c in (_LARGE, _COMM):
+        if c is not None:
+            try:
+                c.close()
+            except Exception:
+                pass
+    _COMM = _LARGE = None
+    _TRIED = _LARGE_TRIED = False
