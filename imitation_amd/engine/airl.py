@@ -39,17 +39,12 @@ from numpy import prod as np_prod
 
 from imitation_amd.algorithms.adversarial import common
 from imitation_amd.algorithms.adversarial.airl import AIRL
-from imitation_amd.engine.gail import DeviceEngineMixin, _FlatParams, _mlp_layers, _policy_nets, supports_generator
+from imitation_amd.engine.gail import DeviceEngineMixin
+from imitation_amd.engine.generator import (OutputNormMixin, _FlatParams, _mlp_layers, _policy_nets, _split,
+                                            rollout_reward_mlp_ok, supports_generator)
 from imitation_amd.parallel import dist as pdist
 from imitation_amd.rewards import reward_nets
 from imitation_amd.util import networks
-
-
-def _split(reward_net) -> Tuple[Any, Any]:
-    """(output normaliser or None, ShapedRewardNet)."""
-    if isinstance(reward_net, reward_nets.NormalizedRewardNet):
-        return reward_net.normalize_output_layer, reward_net.base
-    return None, reward_net
 
 
 def supports(venv, gen_algo, reward_net) -> Tuple[bool, str]:
@@ -67,64 +62,16 @@ def supports(venv, gen_algo, reward_net) -> Tuple[bool, str]:
         return False, "potential is not a BasicPotentialMLP"
     D = int(np_prod(venv.observation_space.shape))
     try:
-        pnorm, plins, _, _ = _mlp_layers(shaped.potential._potential_net)
-        if plins[0].in_features != D or plins[-1].out_features != 1:
-            return False, "potential MLP shape"
-        for seq in (shaped.base.mlp, shaped.potential._potential_net):
-            norm, lins, _, _ = _mlp_layers(seq)
-            if norm is not None and not isinstance(norm, networks.BaseNorm):
-                return False, "unsupported input normaliser"
-            if len(lins) > 4 or max([lins[0].in_features] + [l.out_features for l in lins]) > 64:
-                return False, "reward MLP too wide / deep for the rollout kernel"
+        plins = _mlp_layers(shaped.potential._potential_net)[1]
     except ValueError as e:
         return False, str(e)
+    if plins[0].in_features != D or plins[-1].out_features != 1:
+        return False, "potential MLP shape"
+    for seq in (shaped.base.mlp, shaped.potential._potential_net):
+        ok, why = rollout_reward_mlp_ok(seq)
+        if not ok:
+            return ok, why
     return True, ""
-
-
-class OutputNormMixin:
-    """``NormalizedRewardNet.predict_processed`` (update_stats=True) replayed on device after
-    the rollout kernel: the kernel stores the raw learned reward and the TimeLimit
-    bootstrap; ``reward_outnorm`` normalises step by step in env order and Chan-merges each
-    step's moments (all-reduced once per round under DP)."""
-
-    def _output_norm(self):
-        return _split(self._reward_net)[0]
-
-    def _rollout_extra_bufs(self) -> Dict[str, Any]:
-        out_norm = self._output_norm()
-        if out_norm is None:
-            return {}
-        if not hasattr(self, "_rew_raw"):
-            self._rew_raw = th.zeros(self.T, self.N, device=self._dev)
-            self._onorm_count = th.zeros(1, device=self._dev)
-        return {"rew_raw": self._rew_raw}
-
-    @profiling.traced("rollout/reward_outnorm")
-    def _post_rollout_rewards(self) -> None:
-        out_norm = self._output_norm()
-        if out_norm is None:
-            return
-        step_stats = None
-        if pdist.norm_sync_active():
-            raw = self._rew_raw.double()
-            msg = th.stack([th.full((self.T,), float(self.N), dtype=th.float64, device=self._dev),
-                            raw.sum(1), raw.square().sum(1)], 1).contiguous()
-            pdist.allreduce_sum_(msg)
-            cnt = msg[:, 0]
-            mean = msg[:, 1] / cnt
-            var = (msg[:, 2] / cnt - mean * mean).clamp_min(0.0)
-            step_stats = th.stack([cnt, mean, var], 1).float().contiguous()
-        # an int32 module count is read / written by the kernel itself (no copies around it)
-        direct = out_norm.count.dtype == th.int32
-        if not direct:
-            self._onorm_count.copy_(out_norm.count.reshape(1))
-        self._C.engine_reward_outnorm(dict(T=self.T, N=self.N, rew_raw=self._rew_raw, boot=self._boot,
-                                           rewards=self.buf["rewards"], mean=out_norm.running_mean,
-                                           var=out_norm.running_var, count=self._onorm_count,
-                                           count_i=out_norm.count if direct else None,
-                                           eps=float(out_norm.eps), step_stats=step_stats))
-        if not direct:
-            out_norm.count.copy_(self._onorm_count.to(out_norm.count.dtype).reshape(()))
 
 
 class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
@@ -148,8 +95,6 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
 
     # ------------------------------------------------------------------ fused discriminator (airl_disc.hip)
     def _fused_disc_check(self) -> Tuple[bool, str]:
-        import os
-
         if os.environ.get("IMITATION_AMD_AIRL_FUSED", "1") == "0":
             return False, "disabled (IMITATION_AMD_AIRL_FUSED=0)"
         if type(self).logits_expert_is_high is not AIRL.logits_expert_is_high:

@@ -40,21 +40,11 @@ from imitation_amd.utils import graphs
 from imitation_amd import ops
 from imitation_amd.ops import rl as rl_ops
 from imitation_amd.data import types
+from imitation_amd.engine.generator import _unwrap_native
 from imitation_amd.envs import spaces
 from imitation_amd.parallel import dist as pdist
 from imitation_amd.rl.distributions import CategoricalDistribution, DiagGaussianDistribution
 from imitation_amd.rl.policies import ActorCriticPolicy
-
-
-def _unwrap_native(venv):
-    from imitation_amd.envs.vec_env import NativeVecEnv
-
-    e = venv
-    while e is not None:
-        if isinstance(e, NativeVecEnv):
-            return e
-        e = getattr(e, "venv", None)
-    return None
 
 
 def supports(venv, expert_policy, learner_policy) -> Tuple[bool, str]:

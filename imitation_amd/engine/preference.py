@@ -12,7 +12,7 @@ reference                          this engine
 ``algorithm.learn(steps)``         device rounds: ONE rollout kernel per round (policy
 (collect_rollouts + PPO.train)     + env physics + ``reward_net.predict_processed``,
                                    incl. NormalizedRewardNet output norm), GAE kernel,
-                                   persistent PPO kernel (:mod:`.gail`'s generator core)
+                                   persistent PPO kernel (the :mod:`.generator` core)
 ``BufferingWrapper`` trajectories  the round's (obs, act, env reward, done, terminal
                                    obs) land in pinned host memory with one async copy
                                    that overlaps the PPO kernel; episodes are cut on the
@@ -42,16 +42,10 @@ import torch as th
 
 from imitation_amd.algorithms.preference_comparisons import AgentTrainer, _get_trajectories
 from imitation_amd.data import types
-from imitation_amd.engine.airl import OutputNormMixin
-from imitation_amd.engine.gail import DeviceGeneratorCore, _mlp_layers, supports_generator
+from imitation_amd.engine.generator import (DeviceGeneratorCore, OutputNormMixin, _mlp_layers, _split,
+                                            rollout_reward_mlp_ok, supports_generator)
 from imitation_amd.rewards import reward_nets
 from imitation_amd.util import networks
-
-
-def _split(reward_net) -> Tuple[Any, Any]:
-    if isinstance(reward_net, reward_nets.NormalizedRewardNet):
-        return reward_net.normalize_output_layer, reward_net.base
-    return None, reward_net
 
 
 def _ensemble_of(reward_fn) -> Tuple[Optional[reward_nets.RewardEnsemble], Optional[float]]:
@@ -83,15 +77,7 @@ def supports(venv, algorithm, reward_fn) -> Tuple[bool, str]:
         return False, "output normaliser is not RunningNorm"
     if type(base) is not reward_nets.BasicRewardNet:
         return False, "reward net is not a BasicRewardNet"
-    try:
-        norm, lins, _, _ = _mlp_layers(base.mlp)
-    except ValueError as e:
-        return False, str(e)
-    if norm is not None and not isinstance(norm, networks.BaseNorm):
-        return False, "unsupported input normaliser"
-    if len(lins) > 4 or max([lins[0].in_features] + [l.out_features for l in lins]) > 64:
-        return False, "reward MLP too wide / deep for the rollout kernel"
-    return True, ""
+    return rollout_reward_mlp_ok(base.mlp)
 
 
 class DeviceAgentTrainer(OutputNormMixin, DeviceGeneratorCore, AgentTrainer):
@@ -241,13 +227,9 @@ class DeviceAgentTrainer(OutputNormMixin, DeviceGeneratorCore, AgentTrainer):
         nat = self._native
         self.sync_env_to_host()
         obs0 = nat.reset()
-        st = nat.get_state()
-        self.state.copy_(th.as_tensor(st["state"]).float())
-        self.env_rng.copy_(th.as_tensor(st["rng"].astype(np.int64)))
-        self.elapsed.copy_(th.as_tensor(st["elapsed"].astype(np.int32)))
-        self.cur_obs.copy_(th.as_tensor(np.asarray(obs0, np.float32)).reshape(self.N, self.D))
-        self.cur_start.fill_(1.0)
-        self.ep_ret.zero_()
+        cur = self._env_tensors()  # in place: the static PPO arguments and checkpoints hold these tensors
+        for k, v in self._env_mirror(nat.get_state(), obs0).items():
+            cur[k].copy_(v)
         self._wrapped_ret[:] = 0.0
         self._reset_accumulator()
 
@@ -326,17 +308,8 @@ class DeviceAgentTrainer(OutputNormMixin, DeviceGeneratorCore, AgentTrainer):
         return trajectories
 
     # ------------------------------------------------------------------ checkpoint
-    _ENGINE_TENSORS = ("exp_avg", "exp_avg_sq", "adam_step", "state", "env_rng", "elapsed", "ep_ret", "cur_obs", "cur_start")
-
     def engine_state(self) -> Dict[str, Any]:
-        st: Dict[str, Any] = {k: getattr(self, k).detach().cpu().clone() for k in self._ENGINE_TENSORS}
-        if self.norm_count is not None:
-            if self.pol_norm is not None:  # (the single-rank update keeps the module's count only)
-                self.norm_count.copy_(self.pol_norm.count.reshape(1))
-            st["norm_count"] = self.norm_count.cpu().clone()
-        st.update(step0=int(self._step0), seed=int(self._seed), perm_round=int(self._perm_round),
-                  explore_random=bool(self._explore_random))
-        return st
+        return dict(self._core_engine_state(), explore_random=bool(self._explore_random))
 
     def buffer_state(self) -> Dict[str, Any]:
         """The host-side episode cutter between iterations: finished trajectories not yet
@@ -357,13 +330,7 @@ class DeviceAgentTrainer(OutputNormMixin, DeviceGeneratorCore, AgentTrainer):
         self._wrapped_ret = st["wrapped_ret"].numpy().copy()
 
     def load_engine_state(self, st: Dict[str, Any]) -> None:
-        with th.no_grad():
-            for k in self._ENGINE_TENSORS:
-                getattr(self, k).copy_(st[k].to(self._dev))
-            if self.norm_count is not None and "norm_count" in st:
-                self.norm_count.copy_(st["norm_count"].to(self._dev))
-        self._step0, self._seed = st["step0"], st["seed"]
-        self._perm_round = int(st.get("perm_round", 0))  # the PPO minibatch permutations' round counter
+        self._load_core_engine_state(st)
         self._explore_random = st["explore_random"]
         self._reset_accumulator()
         self.sync_env_to_host()

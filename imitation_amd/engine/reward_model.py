@@ -27,7 +27,7 @@ from imitation_amd.util import networks
 
 def fused_check(trainer) -> Tuple[bool, str]:
     """Whether the reward trainer's minibatch can run on the fused kernels (and why not)."""
-    from imitation_amd.engine.gail import _mlp_layers
+    from imitation_amd.engine.generator import _mlp_layers
 
     if os.environ.get("IMITATION_AMD_PREF_FUSED", "1") == "0":
         return False, "disabled (IMITATION_AMD_PREF_FUSED=0)"
@@ -61,7 +61,7 @@ def fused_check(trainer) -> Tuple[bool, str]:
 def build_plan(trainer, store, L: int, capacity: int):
     """A ``PrefRmPlan`` over the fragment store ``store`` (a ``_MinibatchGraph``)."""
     from imitation_amd import ops
-    from imitation_amd.engine.gail import _mlp_layers
+    from imitation_amd.engine.generator import _mlp_layers
 
     pm = trainer._preference_model
     net = pm.model

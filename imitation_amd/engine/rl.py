@@ -5,7 +5,7 @@ a ``VecNormalize(norm_obs=False)`` venv).
 =================================  ==================================================
 reference                          this engine
 =================================  ==================================================
-``algo.learn(total_timesteps)``    device rounds of the generator core (:mod:`.gail`):
+``algo.learn(total_timesteps)``    device rounds of the generator core (:mod:`.generator`):
 (collect_rollouts + PPO.train)     rollout chain kernel (policy + env physics), parallel
                                    value / log-prob / TimeLimit-bootstrap pass, GAE
                                    kernel, persistent PPO kernel
@@ -32,7 +32,7 @@ from typing import Any, Dict, Mapping, Optional, Tuple
 import numpy as np
 import torch as th
 
-from imitation_amd.engine.gail import DeviceGeneratorCore, supports_generator
+from imitation_amd.engine.generator import DeviceGeneratorCore, supports_generator
 from imitation_amd.envs.vec_env import VecNormalize, is_vecenv_wrapped
 from imitation_amd.ops import rl as rl_ops
 from imitation_amd.parallel import dist as pdist
@@ -181,29 +181,15 @@ class DevicePPO(DeviceGeneratorCore):
         return self
 
     # ------------------------------------------------------------------ checkpoint
-    _ENGINE_TENSORS = ("exp_avg", "exp_avg_sq", "adam_step", "state", "env_rng", "elapsed", "ep_ret", "cur_obs",
-                       "cur_start", "ret", "rms")
+    _ENGINE_TENSORS = DeviceGeneratorCore._ENGINE_TENSORS + ("ret", "rms")
 
     def engine_state(self) -> Dict[str, Any]:
         """Everything a resumed trainer needs beyond the policy's ``state_dict``."""
-        st: Dict[str, Any] = {k: getattr(self, k).detach().cpu().clone() for k in self._ENGINE_TENSORS}
-        if self.norm_count is not None:
-            if self.pol_norm is not None:  # (the single-rank update keeps the module's count only)
-                self.norm_count.copy_(self.pol_norm.count.reshape(1))
-            st["norm_count"] = self.norm_count.cpu().clone()
-        algo = self.gen_algo
-        st.update(step0=int(self._step0), seed=int(self._seed), perm_round=int(self._perm_round),
-                  ep_len=th.as_tensor(self._ep_len.copy()), num_timesteps=int(algo.num_timesteps),
-                  n_updates=int(algo._n_updates))
-        return st
+        return dict(self._core_engine_state(), ep_len=th.as_tensor(self._ep_len.copy()),
+                    num_timesteps=int(self.gen_algo.num_timesteps), n_updates=int(self.gen_algo._n_updates))
 
     def load_engine_state(self, st: Dict[str, Any]) -> None:
-        with th.no_grad():
-            for k in self._ENGINE_TENSORS:
-                getattr(self, k).copy_(st[k].to(self._dev))
-            if self.norm_count is not None and "norm_count" in st:
-                self.norm_count.copy_(st["norm_count"].to(self._dev))
-        self._step0, self._seed, self._perm_round = int(st["step0"]), int(st["seed"]), int(st["perm_round"])
+        self._load_core_engine_state(st)
         self._ep_len = st["ep_len"].numpy().copy()
         self.gen_algo.num_timesteps = int(st["num_timesteps"])
         self.gen_algo._n_updates = int(st["n_updates"])

@@ -69,17 +69,6 @@ def _optimizers(algo) -> Dict[str, th.optim.Optimizer]:
 _ALGO_COUNTERS = ("num_timesteps", "_n_updates", "_episode_num", "_total_timesteps", "_num_timesteps_at_start")
 
 
-def _unwrap_native(venv):
-    from imitation_amd.envs.vec_env import NativeVecEnv
-
-    e = venv
-    while e is not None:
-        if isinstance(e, NativeVecEnv):
-            return e
-        e = getattr(e, "venv", None)
-    return None
-
-
 _PENDING_SEEDS = "__pending_seeds__"
 
 
@@ -87,6 +76,8 @@ def env_state(venv) -> Optional[Dict[str, th.Tensor]]:
     """Native env state, plus the seeds ``venv.seed()`` queued for the next ``reset()`` (-1 =
     none): a fresh env built for the restore has its own queued seeds, which would otherwise
     override the restored RNG at the first reset."""
+    from imitation_amd.engine.generator import _unwrap_native
+
     nat = _unwrap_native(venv)
     if nat is None:
         return None
@@ -96,6 +87,8 @@ def env_state(venv) -> Optional[Dict[str, th.Tensor]]:
 
 
 def load_env_state(venv, st: Optional[Dict[str, th.Tensor]]) -> bool:
+    from imitation_amd.engine.generator import _unwrap_native
+
     nat = _unwrap_native(venv)
     if nat is None or st is None:
         return False

@@ -303,7 +303,7 @@ def _disc_reference(tr, e_idx, g_idx, mb_rows):
 
     import torch.nn.functional as F
 
-    from imitation_amd.engine.gail import _mlp_layers
+    from imitation_amd.engine.generator import _mlp_layers
     from imitation_amd.ops.mlp import tmlp_reference
 
     base = tr._reward_net.base
@@ -532,8 +532,7 @@ def test_device_airl_graphed_disc_matches_eager():
 
 
 def _airl_state(tr, rn):
-    from imitation_amd.engine.airl import _split
-    from imitation_amd.engine.gail import _mlp_layers
+    from imitation_amd.engine.generator import _mlp_layers, _split
 
     _, shaped = _split(rn)
     norms = [_mlp_layers(shaped.base.mlp)[0], _mlp_layers(shaped.potential._potential_net)[0], tr.pol_norm]

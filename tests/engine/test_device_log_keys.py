@@ -10,7 +10,8 @@ import collections
 import numpy as np
 import torch as th
 
-from imitation_amd.engine.gail import DeviceEngineMixin, DeviceGeneratorCore
+from imitation_amd.engine.gail import DeviceEngineMixin
+from imitation_amd.engine.generator import DeviceGeneratorCore
 from imitation_amd.ops import rl as rl_ops
 
 
@@ -48,6 +49,7 @@ class _FakeRound:
         self._last_ppo_info = (T * N, 8)
         self._last_clip_range = 0.2
         self._last_lr = 3e-4
+        self._fps_mark = (None, None)
 
 
 def _host_gen_keys(cartpole_venv, expert_transitions):

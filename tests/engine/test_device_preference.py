@@ -193,7 +193,7 @@ def test_fused_reward_minibatch_matches_autograd(monkeypatch):
     (bf16 operand tolerance); the data-parallel pieces (sums -> forward from the all-reduced
     sums -> reduce-only backward) are the path exercised."""
     from imitation_amd.algorithms import preference_comparisons as pc
-    from imitation_amd.engine.gail import _mlp_layers
+    from imitation_amd.engine.generator import _mlp_layers
     from imitation_amd.ops import preference as pref_ops
 
     venv, frags, prefs = _pref_data()
