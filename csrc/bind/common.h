@@ -42,3 +42,4 @@ void register_wide(py::module& m);
 void register_conv(py::module& m);
 void register_comm(py::module& m);
 void register_pref(py::module& m);
+void register_dqn(py::module& m);

@@ -315,6 +315,34 @@ struct ConvReduceMulti;
 // this launch (the BC step's conv_reduce_multi folded into Adam: bitwise the two launches)
 hipError_t adam_flat(const AdamArgs& a, hipStream_t s, const ConvReduceMulti* red = nullptr);
 
+// ---- dqn_td.hip: every gradient step of one DQN.train call (gather, target, forward, Huber
+// loss, backward, clip, Adam) in one single-workgroup launch
+constexpr int kDqnTdMaxDim = 64;     // obs dim, both hidden widths, actions
+constexpr int kDqnTdMaxBatch = 256;  // rows per gradient step
+struct DqnTdSrc {  // a replay ring viewed as [rows] flat (step * n_envs + env) rows
+  const float *obs, *next_obs;  // [rows, D]
+  const int64_t* action;        // [rows, 1]
+  const float *reward, *done, *timeout;  // [rows]; effective done = done * (1 - timeout)
+  int64_t rows;
+};
+struct DqnTdArgs {
+  DqnTdSrc src[2];  // the agent ring (first n_a rows of a batch) and SQIL's expert ring (last n_e; 0 for plain DQN)
+  const int64_t *ids_a, *ids_b;  // flat row ids [G, n_a], [G, n_e]
+  int G, n_a, n_e;
+  int D, H1, H2, A;  // Q-network: D -> H1 -> H2 -> A with ReLU
+  int off[6];        // offsets of W1, b1, W2, b2, W3, b3 in both flat buckets
+  const float* target;  // the target network's flat bucket
+  // the online FusedAdam bucket of n floats (plain Adam: no weight decay): the kernel updates
+  // params and the moments, advances *step by G and leaves the last step's clipped gradient in grads
+  float *params, *grads, *exp_avg, *exp_avg_sq, *step;
+  int64_t n;
+  float lr, beta1, beta2, eps;
+  float gamma, max_norm;
+  float *losses, *gnorm;  // [G]: Huber loss and pre-clip gradient norm per step
+};
+// hipErrorInvalidValue (nothing launched) outside D, H1, H2, A in 1..64 and n_a + n_e in 1..256
+hipError_t dqn_td_step(const DqnTdArgs& a, hipStream_t s);
+
 // ---- rl.hip: GAE scan over [T, N]
 hipError_t gae_launch(const float* rew, const float* val, const float* starts, const float* last_val, const float* dones,
                       int T, int N, float gamma, float lam, float* adv, float* ret, hipStream_t s,

@@ -9,29 +9,14 @@
 // slot cleared in the same pass (the next backward accumulates into a zeroed bucket).
 #include <hip/hip_runtime.h>
 
+#include "adam_update.h"
 #include "launchers.h"
 #include "wgrad_reduce.h"
 
 namespace ia {
 namespace {
 
-// FMA contraction off, the fused multiply-adds spelled out: the float4 path, the scalar tail and the
-// folded-reduction blocks (one element per thread) then compute bitwise the same update (with
-// contraction left to the compiler, the packed float4 code formed other FMAs than the scalar code).
-__device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v, const AdamArgs& a, float step_size,
-                                         float bc2_sqrt) {
-#pragma clang fp contract(off)
-  float gr = a.maximize ? -g : g;
-  if (a.weight_decay != 0.f) {
-    if (a.decoupled) p *= 1.f - a.lr * a.weight_decay;
-    else gr = __builtin_fmaf(a.weight_decay, p, gr);
-  }
-  m = __builtin_fmaf(1.f - a.beta1, gr - m, m);
-  v = __builtin_fmaf(v, a.beta2, ((1.f - a.beta2) * gr) * gr);
-  const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-  p = __builtin_fmaf(-step_size, m / denom, p);
-  if (a.zero_grad) g = 0.f;
-}
+// (adam_one, the per-element update, and adam_bias: adam_update.h, shared with dqn_td.hip)
 
 // The folded reductions: per layer its weight and bias slot ranges in the flat buffer, and the
 // block range that sums its slab columns.
@@ -50,12 +35,7 @@ template <bool RED>
 __global__ __launch_bounds__(256) void adam_flat_kernel(AdamArgs a, AdamRed rd) {
   // the bias corrections once per block (two powf per thread were ~100 VALU each); same values
   __shared__ float bcs[3];
-  if (threadIdx.x == 0) {
-    const float t0 = *a.step + (a.cnt ? 1.f : 0.f);
-    bcs[0] = t0;
-    bcs[1] = sqrtf(1.f - powf(a.beta2, t0));
-    bcs[2] = a.lr / (1.f - powf(a.beta1, t0));
-  }
+  if (threadIdx.x == 0) adam_bias(a, *a.step + (a.cnt ? 1.f : 0.f), bcs);
   __syncthreads();
   const float t = bcs[0], bc2_sqrt = bcs[1], step_size = bcs[2];
   if (!RED || (int)blockIdx.x >= rd.ncol) {

@@ -81,6 +81,11 @@ class SQILReplayBuffer(buffers.ReplayBuffer):
     def add(self, obs, next_obs, action, reward, done, infos: List[Dict[str, Any]]) -> None:
         super().add(obs=obs, next_obs=next_obs, action=action, reward=np.array(0.0), done=done, infos=infos)
 
+    def td_sources(self, batch_size: int) -> List[Any]:
+        """The agent ring and the expert ring with ``sample``'s half/half row counts."""
+        new_size, expert_size = util.split_in_half(batch_size)
+        return [(self, new_size), (self.expert_buffer, expert_size)]
+
     def sample(self, batch_size: int, env=None) -> buffers.ReplayBufferSamples:
         new_size, expert_size = util.split_in_half(batch_size)
         new_sample = super().sample(new_size, env)

@@ -263,6 +263,17 @@ class ReplayBuffer(BaseBuffer):
         batch_inds = th.randint(0, upper, (batch_size,), device=self.device)
         return self._get_samples(batch_inds, env=env)
 
+    def td_sources(self, batch_size: int) -> List[Any]:
+        """``[(ring, rows)]``: the rings a batch of ``batch_size`` rows is drawn from, in the order
+        of the batch, and how many rows each gives (what ``sample`` would draw)."""
+        return [(self, batch_size)]
+
+    def td_fields(self) -> List[th.Tensor]:
+        """The ring as flat ``step * n_envs + env`` rows: obs, next_obs, actions, rewards, dones, timeouts."""
+        SN = self.buffer_size * self.n_envs
+        return [self.observations.view(SN, *self.obs_shape), self.next_observations.view(SN, *self.obs_shape),
+                self.actions.view(SN, self.action_dim), self.rewards.view(SN), self.dones.view(SN), self.timeouts.view(SN)]
+
     def _get_samples(self, batch_inds: th.Tensor, env=None) -> ReplayBufferSamples:
         from imitation_amd.ops.rl import gather_rows
 

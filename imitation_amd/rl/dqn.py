@@ -6,6 +6,7 @@ replay buffer is device resident and DP averages the Q gradients per step."""
 
 from __future__ import annotations
 
+import os
 from typing import Any, Dict, List, Optional, Tuple, Type, Union
 
 import numpy as np
@@ -101,6 +102,9 @@ class MultiInputPolicy(DQNPolicy):
 
 class DQN(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": DQNPolicy, "CnnPolicy": CnnPolicy, "MultiInputPolicy": MultiInputPolicy}
+    # "fused" (one dqn_td_step launch per train()) or "eager:<reason>"; decided at the first train()
+    td_path: Optional[str] = None
+    _td: Optional[Dict[str, Any]] = None  # the fused step's target bucket and layout
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 32, tau: float = 1.0, gamma: float = 0.99, train_freq=4, gradient_steps: int = 1,
@@ -142,9 +146,118 @@ class DQN(OffPolicyAlgorithm):
         self.exploration_rate = self.exploration_schedule(self._current_progress_remaining)
         self.logger.record("rollout/exploration_rate", self.exploration_rate)
 
+    # ------------------------------------------------------------------ fused TD step
+    def _td_ineligible(self, batch_size: int) -> Optional[str]:
+        """Why this run keeps the autograd TD step (None: the fused one-launch step applies)."""
+        from imitation_amd import ops
+        from imitation_amd.algorithms.sqil import SQILReplayBuffer
+        from imitation_amd.ops import dqn as td
+        from imitation_amd.rl.buffers import ReplayBuffer
+
+        pol = self.policy
+        in_limits = lambda n: 1 <= int(n) <= td.MAX_DIM  # noqa: E731
+        opt = pol.optimizer
+        if os.environ.get("IMITATION_AMD_DQN_FUSED", "1") == "0":
+            return "knob"
+        if not (isinstance(self.observation_space, spaces.Box) and self.observation_space.dtype == np.float32):
+            return "obs-space"
+        if not (pol.features_extractor_class is FlattenExtractor and in_limits(self.q_net.features_dim)):
+            return "features-extractor"
+        if not (len(pol.net_arch) == 2 and all(in_limits(w) for w in pol.net_arch)):
+            return "net-arch"
+        if pol.activation_fn is not nn.ReLU:
+            return "activation"
+        if not (isinstance(self.action_space, spaces.Discrete) and in_limits(self.action_space.n)):
+            return "action-space"
+        g = opt.param_groups[0]
+        if not (pol.optimizer_class is th.optim.Adam and len(opt.param_groups) == 1 and not g.get("amsgrad", False)
+                and g.get("weight_decay", 0.0) == 0.0 and not g.get("maximize", False)
+                and os.environ.get("IMITATION_AMD_FUSED_ADAM", "1") != "0"):  # (the step updates a FusedAdam bucket)
+            return "optimizer"
+        if pdist.world_size() != 1:
+            return "world-size"
+        if type(self.replay_buffer) not in (ReplayBuffer, SQILReplayBuffer):
+            return "replay-buffer"
+        if self._vec_normalize_env is not None:
+            return "vec-normalize"
+        if not 1 <= batch_size <= td.MAX_BATCH:
+            return "batch-size"
+        if not ops.fused_enabled():
+            return "kernels-off"
+        if self.device.type != "cuda":
+            return "device"
+        return None
+
+    def _td_bind(self) -> None:
+        """The fused step's persistent state: the online network in a :class:`FusedAdam` bucket
+        and the target network packed the same way (its parameters views of one flat fp32 buffer,
+        so ``polyak_update`` / ``load_state_dict`` / ``set_parameters`` keep working in place).
+        Checked on every ``train()``: whatever rebound a parameter is packed again."""
+        from imitation_amd.ops import dqn as td
+        from imitation_amd.ops.optim import FusedAdam, to_fused
+
+        def bound(params, flat) -> bool:
+            off = 0
+            for p in params:
+                if p.data_ptr() != flat.data_ptr() + 4 * off:
+                    return False
+                off += p.numel()
+            return True
+
+        online = list(self.q_net.parameters())
+        opt = self.policy.optimizer
+        if not isinstance(opt, FusedAdam):
+            opt = self.policy.optimizer = to_fused(opt)  # (keeps any loaded state)
+            assert isinstance(opt, FusedAdam), "the fused TD step needs the FusedAdam bucket (IMITATION_AMD_FUSED_ADAM=0?)"
+        elif not bound(online, opt._flat[0]["flat"]):
+            sd, g = opt.state_dict(), opt.param_groups[0]
+            opt = self.policy.optimizer = FusedAdam(online, lr=g["lr"], betas=g["betas"], eps=g["eps"])
+            opt.load_state_dict(sd)
+        target = list(self.q_net_target.parameters())
+        if self._td is None or not bound(target, self._td["target"]):
+            n = sum(p.numel() for p in target)
+            flat = th.zeros(n + (-n) % 4, device=self.device)
+            off = 0
+            for p in target:
+                k = p.numel()
+                flat[off : off + k].copy_(p.detach().reshape(-1))
+                p.data = flat[off : off + k].view_as(p)
+                off += k
+            self._td = {"target": flat, "layout": td.TDLayout.from_params(online)}
+
+    def _train_fused(self, gradient_steps: int, batch_size: int) -> None:
+        """All ``gradient_steps`` in one ``dqn_td_step`` launch. The row ids are drawn with the
+        eager path's ``th.randint`` calls in its order (per step: agent step ids, agent env ids,
+        expert step ids, expert env ids), so a seeded run sees the batches the eager run sees."""
+        from imitation_amd.ops import dqn as td
+
+        self._td_bind()
+        f = self.policy.optimizer._flat[0]
+        g = self.policy.optimizer.param_groups[0]
+        sources = self.replay_buffer.td_sources(batch_size)
+        ids = [th.empty((gradient_steps, n), dtype=th.int64, device=self.device) for _, n in sources]
+        for s in range(gradient_steps):
+            for (ring, n), out in zip(sources, ids):
+                th.randint(0, ring.size(), (n,), out=out[s])
+                env_ids = th.randint(0, ring.n_envs, (n,), device=self.device)
+                if ring.n_envs > 1:  # flat row id = step * n_envs + env
+                    th.add(env_ids, out[s], alpha=ring.n_envs, out=out[s])
+        src_b, ids_b = (sources[1][0].td_fields(), ids[1]) if len(sources) > 1 else (None, None)
+        losses, _ = td.dqn_td_step(sources[0][0].td_fields(), src_b, ids[0], ids_b, f["flat"], f["grad"], f["m"], f["v"],
+                                   f["step"], self._td["target"], self._td["layout"], lr=float(g["lr"]), betas=g["betas"],
+                                   eps=g["eps"], gamma=self.gamma, max_norm=self.max_grad_norm)
+        self._n_updates += gradient_steps
+        self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
+        self.logger.record("train/loss", float(losses.mean()))
+
     def train(self, gradient_steps: int, batch_size: int = 100) -> None:
         self.policy.set_training_mode(True)
+        if self.td_path is None:  # decided once, at the first call
+            reason = self._td_ineligible(batch_size)
+            self.td_path = "fused" if reason is None else f"eager:{reason}"
         self._update_learning_rate(self.policy.optimizer)
+        if self.td_path == "fused":
+            return self._train_fused(gradient_steps, batch_size)
         losses = []
         for _ in range(gradient_steps):
             rd = self.replay_buffer.sample(batch_size, env=self._vec_normalize_env)
@@ -180,4 +293,5 @@ class DQN(OffPolicyAlgorithm):
                              tb_log_name=tb_log_name, reset_num_timesteps=reset_num_timesteps, progress_bar=progress_bar)
 
     def _excluded_save_params(self):
-        return super()._excluded_save_params() | {"q_net", "q_net_target", "_q_bucket", "exploration_schedule"}
+        return super()._excluded_save_params() | {"q_net", "q_net_target", "_q_bucket", "exploration_schedule", "td_path",
+                                                   "_td"}
