@@ -1,7 +1,10 @@
-// dqn_td_step: every gradient step of one DQN.train call in one launch (csrc/kernels/dqn_td.hip;
-// imitation_amd/ops/dqn.py). Tensor checks -> raw pointers; the shape limits are the launcher's.
+// dqn_td_step: every gradient step of one DQN.train call in one launch (csrc/kernels/dqn_td.hip);
+// dqn_collect: K steps of acting, env physics and replay-ring writes in one launch
+// (csrc/kernels/dqn_collect.hip). Python side: imitation_amd/ops/dqn.py. Tensor checks -> raw
+// pointers; the shape limits are the launchers'.
 #include "common.h"
 #include "launchers.h"
+#include "vec_env.h"
 
 namespace {
 
@@ -82,6 +85,92 @@ void dqn_td_step(std::vector<torch::Tensor> src_a, c10::optional<std::vector<tor
               " (limits: obs dim, hidden widths, actions in 1..64, batch in 1..256)");
 }
 
+// env: [state [N, sdim], rng [N] int64, elapsed [N] int32, ep_ret [N], cur_obs [N, D]]; ring: the six
+// td_source fields over S * N rows; rec: [done, ep_ret, ep_len int32, action int64], each [K, N]
+void dqn_collect(const std::string& env_id, int64_t max_steps, std::vector<torch::Tensor> env, torch::Tensor act_rng,
+                 std::vector<torch::Tensor> ring, int64_t pos0, int64_t S, torch::Tensor params,
+                 std::vector<int64_t> offsets, int64_t D, int64_t H1, int64_t H2, int64_t A, std::vector<int64_t> thr,
+                 bool use_reward_const, double reward_const, bool write_timeouts, std::vector<torch::Tensor> rec,
+                 c10::optional<torch::Tensor> rec_explore, c10::optional<torch::Tensor> rec_q, torch::Tensor err) {
+  ia::DqnCollectArgs a{};
+  int ms = 0;
+  TORCH_CHECK(ia::make_env_params(env_id, &a.P, &ms), "unknown native env ", env_id);
+  TORCH_CHECK(env.size() == 5, "env: [state, rng, elapsed, ep_ret, cur_obs]");
+  TORCH_CHECK(rec.size() == 4, "records: [done, ep_ret, ep_len, action]");
+  TORCH_CHECK(offsets.size() == 6, "offsets: W1, b1, W2, b2, W3, b3");
+  const int64_t K = (int64_t)thr.size(), N = act_rng.numel();
+  // (the launcher repeats these limits; here they keep the size checks below meaningful)
+  TORCH_CHECK(K >= 1 && K <= ia::kDqnCollectMaxSteps, "dqn_collect: ", hipGetErrorString(hipErrorInvalidValue),
+              " (1..16 steps per launch, got ", K, ")");
+  TORCH_CHECK(N >= 1 && S >= 1 && S * N < (int64_t(1) << 31) && pos0 >= 0 && pos0 < S, "dqn_collect: ring position / size");
+  auto check = [](const torch::Tensor& t, c10::ScalarType dt, int64_t numel, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "dqn_collect: ", name, " must be a contiguous GPU tensor");
+    TORCH_CHECK(t.scalar_type() == dt, "dqn_collect: dtype of ", name);
+    TORCH_CHECK(t.numel() == numel, "dqn_collect: ", name, " has ", t.numel(), " elements, expected ", numel);
+  };
+  a.sdim = ia::state_size(a.P);
+  check(env[0], torch::kFloat32, N * a.sdim, "state");
+  check(env[1], torch::kInt64, N, "rng");
+  check(env[2], torch::kInt32, N, "elapsed");
+  check(env[3], torch::kFloat32, N, "ep_ret");
+  check(env[4], torch::kFloat32, N * D, "cur_obs");
+  check(act_rng, torch::kInt64, N, "act_rng");
+  IA_CHECK_GPU_F32(params);
+  check(err, torch::kInt32, 1, "err");
+  const ia::DqnTdSrc r = td_source(ring, D, "ring");
+  TORCH_CHECK(r.rows == S * N, "dqn_collect: the ring has ", r.rows, " rows, expected S * N = ", S * N);
+  check(rec[0], torch::kFloat32, K * N, "records done");
+  check(rec[1], torch::kFloat32, K * N, "records ep_ret");
+  check(rec[2], torch::kInt32, K * N, "records ep_len");
+  check(rec[3], torch::kInt64, K * N, "records action");
+  if (rec_explore && rec_explore->defined()) {
+    check(*rec_explore, torch::kInt32, K * N, "records explore");
+    a.rec_explore = rec_explore->data_ptr<int>();
+  }
+  if (rec_q && rec_q->defined()) {
+    check(*rec_q, torch::kFloat32, K * N * A, "records q");
+    a.rec_q = rec_q->data_ptr<float>();
+  }
+  a.N = (int)N;
+  a.K = (int)K;
+  a.max_steps = (int)(max_steps < 0 ? ms : max_steps);
+  a.D = (int)D;
+  a.H1 = (int)H1;
+  a.H2 = (int)H2;
+  a.A = (int)A;
+  for (int i = 0; i < 6; ++i) a.off[i] = (int)offsets[i];
+  a.params = params.data_ptr<float>();
+  a.n = params.numel();
+  a.state = env[0].data_ptr<float>();
+  a.rng = reinterpret_cast<uint64_t*>(env[1].data_ptr<int64_t>());
+  a.elapsed = env[2].data_ptr<int>();
+  a.ep_ret = env[3].data_ptr<float>();
+  a.cur_obs = env[4].data_ptr<float>();
+  a.act_rng = reinterpret_cast<uint64_t*>(act_rng.data_ptr<int64_t>());
+  for (int64_t t = 0; t < K; ++t) {
+    TORCH_CHECK(thr[t] >= 0 && thr[t] <= (int64_t(1) << 24), "dqn_collect: thresholds are 24-bit (0 .. 2^24)");
+    a.thr[t] = (uint32_t)thr[t];
+  }
+  a.S = (int)S;
+  a.pos0 = (int)pos0;
+  a.r_obs = const_cast<float*>(r.obs);
+  a.r_next = const_cast<float*>(r.next_obs);
+  a.r_action = const_cast<int64_t*>(r.action);
+  a.r_reward = const_cast<float*>(r.reward);
+  a.r_done = const_cast<float*>(r.done);
+  a.r_timeout = write_timeouts ? const_cast<float*>(r.timeout) : nullptr;
+  a.use_reward_const = use_reward_const ? 1 : 0;
+  a.reward_const = (float)reward_const;
+  a.rec_done = rec[0].data_ptr<float>();
+  a.rec_ep_ret = rec[1].data_ptr<float>();
+  a.rec_ep_len = rec[2].data_ptr<int>();
+  a.rec_action = rec[3].data_ptr<int64_t>();
+  a.err = err.data_ptr<int>();
+  const hipError_t e = ia::dqn_collect(a, ia_stream());
+  TORCH_CHECK(e == hipSuccess, "dqn_collect: ", hipGetErrorString(e),
+              " (limits: 1..16 steps, obs dim, hidden widths, actions in 1..64, a discrete-action vector env of that shape)");
+}
+
 }  // namespace
 
 void register_dqn(py::module& m) {
@@ -90,4 +179,9 @@ void register_dqn(py::module& m) {
         py::arg("offsets"), py::arg("D"), py::arg("H1"), py::arg("H2"), py::arg("A"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("gamma"), py::arg("max_norm"), py::arg("losses"), py::arg("gnorm"),
         "All gradient steps of one DQN.train call (gather, target, forward, Huber loss, backward, clip, Adam) in one launch");
+  m.def("dqn_collect", &dqn_collect, py::arg("env_id"), py::arg("max_steps"), py::arg("env"), py::arg("act_rng"),
+        py::arg("ring"), py::arg("pos0"), py::arg("S"), py::arg("params"), py::arg("offsets"), py::arg("D"), py::arg("H1"),
+        py::arg("H2"), py::arg("A"), py::arg("thr"), py::arg("use_reward_const"), py::arg("reward_const"),
+        py::arg("write_timeouts"), py::arg("rec"), py::arg("rec_explore"), py::arg("rec_q"), py::arg("err"),
+        "K steps of epsilon-greedy acting, env physics and replay-ring writes for N native envs in one launch");
 }

@@ -343,6 +343,45 @@ struct DqnTdArgs {
 // hipErrorInvalidValue (nothing launched) outside D, H1, H2, A in 1..64 and n_a + n_e in 1..256
 hipError_t dqn_td_step(const DqnTdArgs& a, hipStream_t s);
 
+// ---- dqn_collect.hip: K steps of epsilon-greedy acting, env physics and replay-ring writes for N
+// native vector envs in one launch (one wave per env)
+constexpr int kDqnCollectMaxSteps = 16;
+struct DqnCollectArgs {
+  EnvParams P;
+  int N, K;            // envs, steps of this launch (1..16)
+  int max_steps, sdim; // TimeLimit (0: none), floats of env state
+  int D, H1, H2, A;    // Q-network: D -> H1 -> H2 -> A with ReLU (the limits of dqn_td_step)
+  int off[6];          // offsets of W1, b1, W2, b2, W3, b3 in the online flat bucket
+  const float* params; // the online bucket, n floats (read only)
+  int64_t n;
+  // the env block (DeviceGeneratorCore._env_mirror layout), advanced in place
+  float* state;        // [N, sdim]
+  uint64_t* rng;       // [N] the envs' own streams
+  int* elapsed;        // [N]
+  float* ep_ret;       // [N] running episode return
+  float* cur_obs;      // [N, D]
+  uint64_t* act_rng;   // [N] the action streams (splitmix64; explore coin, then the random action)
+  uint32_t thr[kDqnCollectMaxSteps];  // step t explores iff its 24-bit draw < thr[t] (2^24: always)
+  // the replay ring: S step slots of N rows, step t goes to slot (pos0 + t) % S, flat row slot * N + n
+  int S, pos0;
+  float *r_obs, *r_next;  // [S * N, D]
+  int64_t* r_action;      // [S * N]
+  float *r_reward, *r_done;
+  float* r_timeout;       // null: not written (a ring without handle_timeout_termination)
+  int use_reward_const;   // store reward_const instead of the env reward (SQIL's agent ring)
+  float reward_const;
+  // per-step records [K, N]
+  float *rec_done, *rec_ep_ret;  // ep_ret: the episode's return where it ended, else 0
+  int* rec_ep_len;               // the episode's length where it ended, else 0
+  int64_t* rec_action;           // the executed action
+  int* rec_explore;              // optional: 1 where the step explored
+  float* rec_q;                  // optional: [K, N, A] the Q-values the greedy action came from
+  int* err;                      // error word: bit 0 is set when a Q-value is not finite (the step acts 0)
+};
+// hipErrorInvalidValue (nothing launched) outside K in 1..16, D, H1, H2, A in 1..64, for an env that is
+// not a discrete-action vector env of these D and A, and for a threshold above 2^24
+hipError_t dqn_collect(const DqnCollectArgs& a, hipStream_t s);
+
 // ---- rl.hip: GAE scan over [T, N]
 hipError_t gae_launch(const float* rew, const float* val, const float* starts, const float* last_val, const float* dones,
                       int T, int N, float gamma, float lam, float* adv, float* ret, hipStream_t s,

@@ -8,6 +8,7 @@ replay rings; the expert half is bulk-uploaded once.
 
 from __future__ import annotations
 
+import logging
 from typing import Any, Dict, List, Optional, Type, Union
 
 import numpy as np
@@ -26,7 +27,13 @@ class SQIL(algo_base.DemonstrationAlgorithm[types.Transitions]):
 
     def __init__(self, *, venv, demonstrations: Optional[algo_base.AnyTransitions], policy,
                  custom_logger: Optional[logger.HierarchicalLogger] = None, rl_algo_class=DQN,
-                 rl_kwargs: Optional[Dict[str, Any]] = None):
+                 rl_kwargs: Optional[Dict[str, Any]] = None, engine: str = "host"):
+        """``engine``: ``"host"`` trains with the learner's own ``learn`` loop; ``"device"`` with
+        :class:`imitation_amd.engine.dqn.DeviceDQN` (acting, env stepping and replay writes on the
+        GPU; ``ValueError`` with the reason when the run is not eligible); ``"auto"`` uses the
+        device engine when eligible and the host loop otherwise."""
+        if engine not in ("host", "device", "auto"):
+            raise ValueError(f"SQIL engine must be 'host', 'device' or 'auto', not {engine!r}")
         self.venv = venv
         if rl_kwargs is None:
             rl_kwargs = {}
@@ -37,13 +44,30 @@ class SQIL(algo_base.DemonstrationAlgorithm[types.Transitions]):
         self.rl_algo = rl_algo_class(policy=policy, env=venv, replay_buffer_class=SQILReplayBuffer,
                                      replay_buffer_kwargs={"demonstrations": demonstrations}, **rl_kwargs)
         super().__init__(demonstrations=demonstrations, custom_logger=custom_logger)
+        self._engine = None
+        if engine != "host":
+            from imitation_amd.engine import dqn as dqn_engine
+
+            ok, why = dqn_engine.supports(venv, self.rl_algo)
+            if ok:
+                self._engine = dqn_engine.DeviceDQN(self.rl_algo, venv)
+            elif engine == "device":
+                raise ValueError(f"SQIL engine='device' is not applicable: {why}")
+            else:
+                logging.getLogger(__name__).info("SQIL: host loop (device engine not applicable: %s)", why)
+
+    @property
+    def engine_kind(self) -> str:
+        """``"device"`` when :meth:`train` runs the device engine, else ``"host"``."""
+        return "host" if self._engine is None else "device"
 
     def set_demonstrations(self, demonstrations: algo_base.AnyTransitions) -> None:
         assert isinstance(self.rl_algo.replay_buffer, SQILReplayBuffer)
         self.rl_algo.replay_buffer.set_demonstrations(demonstrations)
 
     def train(self, *, total_timesteps: int, tb_log_name: str = "SQIL", **kwargs: Any):
-        self.rl_algo.learn(total_timesteps=total_timesteps, tb_log_name=tb_log_name, **kwargs)
+        learner = self.rl_algo if self._engine is None else self._engine
+        learner.learn(total_timesteps=total_timesteps, tb_log_name=tb_log_name, **kwargs)
 
     @property
     def policy(self):

@@ -9,12 +9,22 @@ and Adam -- ``csrc/kernels/dqn_td.hip``, one workgroup, all fp32.
 ``dqn_td_reference`` is the same ``G`` steps in plain torch ops on the same buckets and row
 ids (any float dtype, CPU or GPU): the numerics oracle of the kernel tests and what
 ``dqn_td_step`` runs for CPU tensors.
+
+Device-resident collection: ``dqn_collect`` advances ``N`` native vector envs by ``K <= 16`` steps
+in ONE launch (``csrc/kernels/dqn_collect.hip``, one wave per env): Q forward from the online
+bucket, greedy action, epsilon-greedy from a per-env ``splitmix64`` action stream (integer-exact
+24-bit draws against the thresholds of :func:`explore_thresholds`), env step with TimeLimit and
+auto-reset, and the replay-ring row. ``dqn_collect_reference`` replays a recorded action
+sequence in torch ops through the ``dagger_env_step`` binding (the same device-compiled
+physics): the oracle of the kernel tests. :func:`splitmix64`, :func:`seed_stream` and
+:func:`explore_draws` mirror ``csrc/include/ia/rng.h`` and the kernel's draws in Python ints.
 """
 
 from __future__ import annotations
 
 import dataclasses
-from typing import Optional, Sequence, Tuple
+import math
+from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch as th
 
@@ -154,3 +164,171 @@ def dqn_td_step(src_a: Source, src_b: Optional[Source], ids_a: th.Tensor, ids_b:
                              float(lr), float(betas[0]), float(betas[1]), float(eps), float(gamma), float(max_norm),
                              losses, gnorm)
     return losses, gnorm
+
+
+# ---------------------------------------------------------------------- device-resident collection
+MAX_COLLECT_STEPS = 16  # steps per dqn_collect launch
+EXPLORE_ALWAYS = 1 << 24  # the threshold at which every 24-bit draw explores
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(state: int) -> Tuple[int, int]:
+    """``ia::splitmix64`` on masked 64-bit ints: ``(new state, output)``."""
+    state = (state + 0x9E3779B97F4A7C15) & _M64
+    z = state
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return state, z ^ (z >> 31)
+
+
+def seed_stream(seed: int, stream: int) -> int:
+    """``ia::seed_stream``: the initial state of stream ``stream`` of ``seed``."""
+    s = ((seed & _M64) ^ (0xD1B54A32D192ED03 * (stream + 1))) & _M64
+    return splitmix64(s)[0]
+
+
+def draw24(state: int) -> Tuple[int, int]:
+    """One 24-bit draw (``splitmix64(s) >> 40``): ``(new state, draw)``."""
+    state, z = splitmix64(state)
+    return state, z >> 40
+
+
+def explore_draws(state: int, thr: Sequence[int], n_actions: int) -> Tuple[List[bool], List[Optional[int]], int]:
+    """The kernel's draws of one env over ``len(thr)`` steps from the action-stream ``state``:
+    ``(explore flags, random actions (None where the step is greedy), state after the launch)``."""
+    flags: List[bool] = []
+    acts: List[Optional[int]] = []
+    for th_t in thr:
+        state, u = draw24(state)
+        explore = u < th_t
+        act = None
+        if explore:
+            state, v = draw24(state)
+            act = (v * n_actions) >> 24
+        flags.append(explore)
+        acts.append(act)
+    return flags, acts, state
+
+
+def explore_thresholds(eps: Sequence[float]) -> List[int]:
+    """24-bit thresholds of exploration rates: ``floor(eps * 2^24)`` in fp64, clamped to
+    ``0 .. 2^24`` (a step explores iff its draw is below; ``2^24``: every draw explores)."""
+    return [min(EXPLORE_ALWAYS, max(0, int(math.floor(float(e) * EXPLORE_ALWAYS)))) for e in eps]
+
+
+def _as_i64(v: int) -> int:
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _as_u64(v: int) -> int:
+    return v & _M64
+
+
+def action_streams(seed: int, n: int, device) -> th.Tensor:
+    """``act_rng [n]`` int64 (the bits of ``seed_stream(seed, i)``) for :func:`dqn_collect`."""
+    return th.tensor([_as_i64(seed_stream(int(seed), i)) for i in range(n)], dtype=th.int64, device=device)
+
+
+def stream_states(act_rng: th.Tensor) -> List[int]:
+    """The unsigned 64-bit states held by an ``act_rng`` / env ``rng`` tensor."""
+    return [_as_u64(int(v)) for v in act_rng.cpu().tolist()]
+
+
+def collect_records(K: int, N: int, A: int, device, explore: bool = False, q: bool = False) -> Dict[str, th.Tensor]:
+    """The per-step records ``[K, N]`` of one launch: ``done``, ``ep_ret`` and ``ep_len`` (0 unless
+    the episode ended), the executed ``action``; on request the ``explore`` flag and ``q [K, N, A]``."""
+    rec = dict(done=th.zeros(K, N, device=device), ep_ret=th.zeros(K, N, device=device),
+               ep_len=th.zeros(K, N, dtype=th.int32, device=device), action=th.zeros(K, N, dtype=th.int64, device=device))
+    if explore:
+        rec["explore"] = th.zeros(K, N, dtype=th.int32, device=device)
+    if q:
+        rec["q"] = th.zeros(K, N, A, device=device)
+    return rec
+
+
+_ENV_KEYS = ("state", "rng", "elapsed", "ep_ret", "cur_obs")
+
+
+def dqn_collect(env: Mapping[str, Any], ring_fields: Source, pos0: int, S: int, flat: th.Tensor, layout: TDLayout,
+                thr: Sequence[int], act_rng: th.Tensor, reward_const: Optional[float] = None,
+                write_timeouts: bool = True, records: Optional[Dict[str, th.Tensor]] = None,
+                err: Optional[th.Tensor] = None) -> Dict[str, th.Tensor]:
+    """``K = len(thr)`` env steps of ``N = len(act_rng)`` native envs in ONE kernel launch.
+
+    ``env``: the env block (``state``, ``rng``, ``elapsed``, ``ep_ret``, ``cur_obs`` as
+    ``DeviceGeneratorCore._env_mirror`` lays them out, plus ``env``: the native env id and
+    ``max_steps``), advanced in place. ``ring_fields``: ``ReplayBuffer.td_fields()`` of a ring of
+    ``S`` step slots; step ``t`` goes to slot ``(pos0 + t) % S``. ``flat`` / ``layout``: the online
+    bucket. ``reward_const``: stored instead of the env reward (SQIL's agent ring: 0);
+    ``write_timeouts=False`` leaves the ring's ``timeouts`` alone (a ring without
+    ``handle_timeout_termination``). ``err``: int32 error word (bit 0: a non-finite Q-value).
+    Returns ``records`` (:func:`collect_records`; allocated when None). GPU tensors only."""
+    if not flat.is_cuda:
+        raise ValueError("dqn_collect runs on the GPU only (dqn_collect_reference replays recorded actions)")
+    K, N = len(thr), int(act_rng.numel())
+    if records is None:
+        records = collect_records(K, N, layout.A, flat.device)
+    if err is None:
+        err = th.zeros(1, dtype=th.int32, device=flat.device)
+    ops.native().dqn_collect(str(env["env"]), int(env["max_steps"]), [env[k] for k in _ENV_KEYS], act_rng,
+                             list(ring_fields), int(pos0), int(S), flat, list(layout.offsets), layout.D, layout.H1,
+                             layout.H2, layout.A, [int(t) for t in thr], reward_const is not None,
+                             float(reward_const or 0.0), bool(write_timeouts),
+                             [records[k] for k in ("done", "ep_ret", "ep_len", "action")], records.get("explore"),
+                             records.get("q"), err)
+    return records
+
+
+def q_values(obs: th.Tensor, flat: th.Tensor, layout: TDLayout) -> th.Tensor:
+    """``Q(obs)`` of the bucket's network in torch ops, in the dtype of ``flat``."""
+    W1, b1, W2, b2, W3, b3 = layout.views(flat)
+    return th.relu(th.relu(obs.to(flat.dtype) @ W1.T + b1) @ W2.T + b2) @ W3.T + b3
+
+
+def dqn_collect_reference(env: Mapping[str, Any], ring_fields: Source, pos0: int, S: int, flat: th.Tensor,
+                          layout: TDLayout, actions: th.Tensor, reward_const: Optional[float] = None,
+                          write_timeouts: bool = True,
+                          records: Optional[Dict[str, th.Tensor]] = None) -> Dict[str, th.Tensor]:
+    """The ``K`` steps of :func:`dqn_collect` in torch ops for the recorded ``actions [K, N]``:
+    per step Q with torch (into ``records["q"]``), the action through the ``dagger_env_step``
+    binding (the device-compiled physics of the kernel) and the ring rows by torch indexing.
+    Advances ``env`` and the ring in place; returns the records (``action`` = ``actions``)."""
+    C = ops.native()
+    K, N = int(actions.shape[0]), int(actions.shape[1])
+    dev = flat.device
+    if records is None:
+        records = collect_records(K, N, layout.A, dev, q=True)
+    r_obs, r_next, r_act, r_rew, r_done, r_tmo = ring_fields
+    cur = env["cur_obs"]
+    rew = th.zeros(N, device=dev)
+    term = th.zeros(N, dtype=th.uint8, device=dev)
+    trunc = th.zeros(N, dtype=th.uint8, device=dev)
+    term_obs = th.zeros_like(cur)
+    ep_ret_out = th.zeros(N, device=dev)
+    ep_len_out = th.zeros(N, dtype=th.int32, device=dev)
+    lanes = th.arange(N, device=dev)
+    for t in range(K):
+        x = cur.clone()
+        if "obs" in records:  # (the pre-step observations [K, N, D], for an fp64 evaluation of q)
+            records["obs"][t].copy_(x)
+        if "q" in records:
+            records["q"][t].copy_(q_values(x, flat, layout))
+        a_t = actions[t].to(th.int64).contiguous()
+        C.dagger_env_step(dict(env=str(env["env"]), N=N, max_steps=int(env["max_steps"]), mode=0, state=env["state"],
+                               rng=env["rng"], elapsed=env["elapsed"], ep_ret=env["ep_ret"], obs=cur, actions=a_t,
+                               rew=rew, term=term, trunc=trunc, term_obs=term_obs, ep_ret_out=ep_ret_out,
+                               ep_len_out=ep_len_out))
+        done = (term | trunc) > 0
+        rows = ((pos0 + t) % S) * N + lanes
+        r_obs[rows] = x.reshape(N, *r_obs.shape[1:])
+        r_next[rows] = th.where(done.reshape(N, 1), term_obs, cur).reshape(N, *r_next.shape[1:])
+        r_act[rows] = a_t.reshape(N, *r_act.shape[1:])
+        r_rew[rows] = th.full_like(rew, float(reward_const)) if reward_const is not None else rew
+        r_done[rows] = done.float()
+        if write_timeouts:
+            r_tmo[rows] = (trunc > 0).float()
+        records["done"][t] = done.float()
+        records["ep_ret"][t] = ep_ret_out
+        records["ep_len"][t] = ep_len_out
+        records["action"][t] = a_t
+    return records

@@ -225,10 +225,12 @@ class DQN(OffPolicyAlgorithm):
                 off += k
             self._td = {"target": flat, "layout": td.TDLayout.from_params(online)}
 
-    def _train_fused(self, gradient_steps: int, batch_size: int) -> None:
-        """All ``gradient_steps`` in one ``dqn_td_step`` launch. The row ids are drawn with the
-        eager path's ``th.randint`` calls in its order (per step: agent step ids, agent env ids,
-        expert step ids, expert env ids), so a seeded run sees the batches the eager run sees."""
+    def _td_launch(self, gradient_steps: int, batch_size: int) -> th.Tensor:
+        """All ``gradient_steps`` in one ``dqn_td_step`` launch; returns the device ``losses``
+        ``[gradient_steps]`` (no host read: the device engine keeps them there). The row ids are
+        drawn with the eager path's ``th.randint`` calls in its order (per step: agent step ids,
+        agent env ids, expert step ids, expert env ids), so a seeded run sees the batches the
+        eager run sees."""
         from imitation_amd.ops import dqn as td
 
         self._td_bind()
@@ -246,6 +248,10 @@ class DQN(OffPolicyAlgorithm):
         losses, _ = td.dqn_td_step(sources[0][0].td_fields(), src_b, ids[0], ids_b, f["flat"], f["grad"], f["m"], f["v"],
                                    f["step"], self._td["target"], self._td["layout"], lr=float(g["lr"]), betas=g["betas"],
                                    eps=g["eps"], gamma=self.gamma, max_norm=self.max_grad_norm)
+        return losses
+
+    def _train_fused(self, gradient_steps: int, batch_size: int) -> None:
+        losses = self._td_launch(gradient_steps, batch_size)
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         self.logger.record("train/loss", float(losses.mean()))

@@ -12,6 +12,9 @@ sqil_ingredient = Ingredient("sqil", ingredients=[rl.rl_ingredient, policy.polic
 def config():
     total_timesteps = 3e5
     train_kwargs = dict(log_interval=4, progress_bar=False)
+    # "host": the learner's own loop; "device": acting, env stepping and replay writes on the GPU
+    # (engine/dqn.py; an error when the run is not eligible); "auto": device when eligible
+    engine = "host"
     locals()
 
 

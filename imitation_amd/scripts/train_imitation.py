@@ -131,7 +131,9 @@ def sqil(sqil: Mapping[str, Any], policy: Mapping[str, Any], rl: Mapping[str, An
     expert_trajs = demonstrations.get_expert_trajectories()
     with environment.make_venv() as venv:
         trainer = sqil_algorithm.SQIL(venv=venv, demonstrations=expert_trajs, policy=policy["policy_cls"],
-                                      custom_logger=custom_logger, rl_algo_class=rl["rl_cls"], rl_kwargs=rl["rl_kwargs"])
+                                      custom_logger=custom_logger, rl_algo_class=rl["rl_cls"], rl_kwargs=rl["rl_kwargs"],
+                                      engine=sqil.get("engine", "host"))
+        logger.info("sqil: %s engine", trainer.engine_kind)
         with watchdog.cli_watchdog("train_imitation") as wd:
             train_kwargs = dict(sqil["train_kwargs"])
             if "callback" not in train_kwargs:
