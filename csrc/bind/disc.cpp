@@ -96,7 +96,7 @@ class DiscPlan {
     g_.shift = desc_.norm_mean;
     g_.X = fptr("X");
     g_.partials = fptr("partials");
-    TORCH_CHECK(held_.back().numel() >= (int64_t)ia::disc_gather_blocks(mb_) * 2 * g_.din, "partials too small");
+    TORCH_CHECK(held_.back().numel() >= (int64_t)ia::disc_partials_floats(mb_, g_.din), "partials too small");
 
     // norms
     n_ = ia::DiscNormArgs{};
@@ -104,6 +104,7 @@ class DiscPlan {
     n_.din = g_.din;
     n_.nblk = ia::disc_gather_blocks(mb_);
     n_.partials = g_.partials;
+    n_.X = g_.X;
     n_.shift = desc_.norm_mean;
     n_.rew_mean = const_cast<float*>(desc_.norm_mean);
     n_.rew_var = const_cast<float*>(desc_.norm_var);
@@ -164,6 +165,7 @@ class DiscPlan {
   void gather(int k, torch::Tensor e_idx, torch::Tensor g_idx) {
     check_idx(e_idx);
     check_idx(g_idx);
+    TORCH_CHECK(k >= 0 && k < n_mb_, "minibatch ", k, " out of range");
     ia::DiscGatherArgs g = g_;
     g.e_idx = e_idx.data_ptr<int64_t>() + (size_t)k * mb_;
     g.g_idx = g_idx.data_ptr<int64_t>() + (size_t)k * mb_;
@@ -193,6 +195,7 @@ class DiscPlan {
     IA_HIP_CHECK3(ia::disc_norm(n, ia_stream()));
   }
   void fwd_bwd(int k) {
+    TORCH_CHECK(k >= 0 && k < n_mb_, "minibatch ", k, " out of range");
     ia::DiscLoss dl{mb_, scale_, stats_slab_ + (size_t)k * fb_blocks_ * ia::kDiscStats};
     IA_HIP_CHECK3(ia::tmlp_disc_fwd_bwd(desc_, g_.X, 2 * mb_, dl, slab_ + (size_t)k * fb_blocks_ * n_params_, ia_stream()));
   }
@@ -242,6 +245,7 @@ class DiscPlan {
 };
 
 // Workspace sizes for a configuration: (gather blocks, fwd/bwd blocks per minibatch, n_params).
+// `partials` holds 4 * din floats per gather block (two pairs of moment sums, see disc.hip).
 py::tuple disc_plan_sizes(std::vector<int> dims, int minibatch) {
   ia::MLPDesc d{};
   d.n_layers = (int)dims.size() - 1;

@@ -27,6 +27,7 @@ namespace ia {
 namespace {
 
 constexpr int kGatherRows = 64;  // rows per gather block (>= 256 blocks for a 16k batch)
+constexpr int kMomentSums = 4;   // per block and column: S1, S2 under two shifts (disc_gather_kernel)
 
 __device__ __forceinline__ float load_act(const DiscGatherArgs& a, bool expert, int64_t src, int j, int aw) {
   if (a.act_discrete) {
@@ -55,15 +56,31 @@ __device__ __forceinline__ float gather_col(const DiscGatherArgs& a, bool expert
   return (expert ? a.e_dones : a.g_dones)[src] ? 1.f : 0.f;
 }
 
+// Shift of the moment sums. The batch variance is formed as S2/n - (S1/n)^2 from fp32 block
+// sums of (v - shift) and (v - shift)^2, which is only accurate when |mean - shift| is not
+// large against the column's spread (a column at 100 +- 1 summed with shift 0 loses three
+// digits of its variance). The running mean is such a shift once it has seen data, but it is
+// 0 on the first update and absent when the reward net has no input normaliser. So every
+// block keeps two pairs of sums: one shifted by the running mean (or 0), one shifted by the
+// minibatch's own first gathered row, which each block re-gathers and disc_norm reads back
+// from X row 0. disc_norm takes the running-mean pair unless the two variances disagree (see
+// there), so well-centred data gives the bits it always gave.
+// The DP modes all-reduce the sums over ranks and need a shift every rank agrees on: they
+// use the running-mean pair alone. Remaining limitation: there, until the running mean has
+// seen data -- or always, without a reward normaliser -- an off-centre column's variance keeps
+// that cancellation error.
+//
 // Block: 256 threads = 2 row phases x 128 columns; rows [blk*64, blk*64+64).
+// partials[blk] = [S1, S2 (running-mean shift), S1, S2 (row-0 shift)][din]
 __global__ __launch_bounds__(256) void disc_gather_kernel(DiscGatherArgs a) {
-  __shared__ float red[2][2][128];
+  __shared__ float red[2][4][128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
   const int n = 2 * a.mb;
   const int r0 = blockIdx.x * kGatherRows;
   const bool col_ok = c < a.din;
   const float shift = col_ok && a.shift ? a.shift[c] : 0.f;
-  float s1 = 0.f, s2 = 0.f;
+  const float shift0 = col_ok ? gather_col(a, true, a.e_idx[0], c) : 0.f;
+  float s1 = 0.f, s2 = 0.f, d1 = 0.f, d2 = 0.f;
   if (col_ok) {
     for (int rr = ph; rr < kGatherRows; rr += 2) {
       const int r = r0 + rr;
@@ -75,15 +92,20 @@ __global__ __launch_bounds__(256) void disc_gather_kernel(DiscGatherArgs a) {
       const float dv = v - shift;
       s1 += dv;
       s2 += dv * dv;
+      const float dv0 = v - shift0;
+      d1 += dv0;
+      d2 += dv0 * dv0;
     }
   }
   red[ph][0][c] = s1;
   red[ph][1][c] = s2;
+  red[ph][2][c] = d1;
+  red[ph][3][c] = d2;
   __syncthreads();
   if (ph == 0 && col_ok) {
-    float* out = a.partials + (size_t)blockIdx.x * 2 * a.din;
-    out[c] = red[0][0][c] + red[1][0][c];
-    out[a.din + c] = red[0][1][c] + red[1][1][c];
+    float* out = a.partials + (size_t)blockIdx.x * kMomentSums * a.din;
+#pragma unroll
+    for (int k = 0; k < kMomentSums; ++k) out[k * a.din + c] = red[0][k][c] + red[1][k][c];
   }
 }
 
@@ -102,44 +124,82 @@ __device__ __forceinline__ void chan_merge(float* rmean, float* rvar, int count,
 // order, then the 8 phase sums are added in phase order (fixed order: deterministic).
 constexpr int kNormPhases = 8;
 
+// Phase ph's sums of the first NS partial rows of blocks ph, ph + 8, ... for one column, added
+// in block order; the loads of four blocks are issued together (the loop is latency-bound).
+template <int NS>
+__device__ __forceinline__ void sum_partials(const float* __restrict__ p, int ph, int nblk, int din,
+                                             double (&s)[kMomentSums]) {
+  constexpr int U = 4;
+  const size_t step = (size_t)kNormPhases * kMomentSums * din;
+  int b = ph;
+  for (; b + (U - 1) * kNormPhases < nblk; b += U * kNormPhases, p += U * step) {
+    float v[U][NS];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int k = 0; k < NS; ++k) v[u][k] = p[u * step + (size_t)k * din];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int k = 0; k < NS; ++k) s[k] += (double)v[u][k];
+  }
+  for (; b < nblk; b += kNormPhases, p += step)
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] += (double)p[(size_t)k * din];
+}
+
+// The two variances of a column (see disc_gather_kernel) agree to rounding when the running
+// mean is a fair centre of the batch; then the running-mean pair is used, as it always was.
+// Where they differ by more than kMomentRtol of the row-0 variance, the running-mean pair
+// has lost that much to cancellation and the row-0 pair, whose error stays near fp32
+// rounding whatever the column's offset, is used instead.
+constexpr double kMomentRtol = 1e-5;
+
 __global__ __launch_bounds__(128 * kNormPhases) void disc_norm_kernel(DiscNormArgs a) {
-  __shared__ double red[kNormPhases][2][128];
+  __shared__ double red[kNormPhases][kMomentSums][128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
   const int n = a.mode == 2 ? a.n_total : 2 * a.mb;
   const int rc = a.rew_count ? *a.rew_count : 0;
   const int pc = a.pol_count ? *a.pol_count : 0;
   if (a.mode != 2) {
-    double s1 = 0.0, s2 = 0.0;
-    if (c < a.din)
-      for (int b = ph; b < a.nblk; b += kNormPhases) {
-        const float* p = a.partials + (size_t)b * 2 * a.din;
-        s1 += (double)p[c];
-        s2 += (double)p[a.din + c];
-      }
-    red[ph][0][c] = s1;
-    red[ph][1][c] = s2;
+    double s[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
+    if (c < a.din) {
+      const float* p = a.partials + (size_t)ph * kMomentSums * a.din + c;
+      if (a.mode == 0) sum_partials<kMomentSums>(p, ph, a.nblk, a.din, s);
+      else sum_partials<2>(p, ph, a.nblk, a.din, s);  // the DP sums carry the shared shift only
+    }
+#pragma unroll
+    for (int k = 0; k < kMomentSums; ++k) red[ph][k][c] = s[k];
     __syncthreads();
   }
   if (ph == 0 && c < a.din) {
-    double S1 = 0.0, S2 = 0.0;
+    double S[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
     if (a.mode == 2) {
-      S1 = a.sums[c];
-      S2 = a.sums[a.din + c];
+      S[0] = a.sums[c];
+      S[1] = a.sums[a.din + c];
     } else {
-      for (int q = 0; q < kNormPhases; ++q) {
-        S1 += red[q][0][c];
-        S2 += red[q][1][c];
-      }
+      for (int q = 0; q < kNormPhases; ++q)
+#pragma unroll
+        for (int k = 0; k < kMomentSums; ++k) S[k] += red[q][k][c];
     }
     if (a.mode == 1) {
-      a.sums[c] = S1;
-      a.sums[a.din + c] = S2;
+      a.sums[c] = S[0];
+      a.sums[a.din + c] = S[1];
     } else {
       const double shift = a.shift ? (double)a.shift[c] : 0.0;
-      const double m = S1 / n;
-      double var = S2 / n - m * m;
+      const double m = S[0] / n;
+      double var = S[1] / n - m * m;
       if (var < 0.0) var = 0.0;
-      const float bmean = (float)(shift + m), bvar = (float)var;
+      float bmean = (float)(shift + m), bvar = (float)var;
+      if (a.mode == 0) {
+        const double m0 = S[2] / n;
+        double var0 = S[3] / n - m0 * m0;
+        if (var0 < 0.0) var0 = 0.0;
+        if (fabs(var - var0) > kMomentRtol * var0) {
+          bmean = (float)((double)a.X[c] + m0);
+          bvar = (float)var0;
+        }
+      }
       if (a.rew_mean) chan_merge(a.rew_mean, a.rew_var, rc, c, bmean, bvar, n);
       if (a.pol_defer && c < a.pol_cols) {
         a.pol_defer[c] = bmean;
@@ -242,6 +302,7 @@ __global__ __launch_bounds__(64 * kAdamPhases) void disc_adam_kernel(DiscAdamArg
 }  // namespace
 
 int disc_gather_blocks(int mb) { return (2 * mb + kGatherRows - 1) / kGatherRows; }
+size_t disc_partials_floats(int mb, int din) { return (size_t)disc_gather_blocks(mb) * kMomentSums * din; }
 
 hipError_t disc_gather(const DiscGatherArgs& a, hipStream_t s) {
   if (a.din > 128 || a.din <= 0) return hipErrorInvalidValue;
@@ -250,7 +311,7 @@ hipError_t disc_gather(const DiscGatherArgs& a, hipStream_t s) {
 }
 
 hipError_t disc_norm(const DiscNormArgs& a, hipStream_t s) {
-  if (a.din > 128) return hipErrorInvalidValue;
+  if (a.din > 128 || (a.mode == 0 && a.X == nullptr)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(disc_norm_kernel, dim3(1), dim3(128 * kNormPhases), 0, s, a);
   return hipGetLastError();
 }

@@ -13,7 +13,9 @@
 namespace ia {
 
 // ---- tmlp.hip: fused tiny-MLP
-int tmlp_waves_for(const MLPDesc& d);
+// static_lds: bytes of __shared__ arrays the 4-wave instance declares besides the
+// dynamic image (they count against the same 160 KiB)
+int tmlp_waves_for(const MLPDesc& d, int static_lds = 0);
 size_t tmlp_slab_floats(const MLPDesc& d, int B);
 hipError_t tmlp_forward(const MLPDesc& d, const float* X, int B, float* Y, hipStream_t s);
 hipError_t tmlp_backward(const MLPDesc& d, const float* X, const float* dY, int B, float* dX, const MLPGrads& g,
@@ -40,7 +42,7 @@ struct DiscGatherArgs {
   const bool* g_dones;
   const float* shift;  // per-column shift for the moment sums (running mean) or null
   float* X;            // [2*mb][din]
-  float* partials;     // [nblk][2][din]
+  float* partials;     // [nblk][4][din]: S1, S2 shifted by `shift`, S1, S2 shifted by X row 0
 };
 struct DiscNormArgs {
   int mode;  // 0: reduce partials + merge; 1: reduce partials -> sums only; 2: merge from sums
@@ -49,6 +51,7 @@ struct DiscNormArgs {
   int n_total;   // rows behind sums (mode 2: all DP ranks)
   const float* partials;
   const float* shift;
+  const float* X;   // [2*mb][din] gathered minibatch (mode 0: row 0 is the second shift)
   float *rew_mean, *rew_var;
   int* rew_count;
   int pol_cols;
@@ -75,6 +78,7 @@ struct DiscAdamArgs {
   float stats_scale;  // stats_out = scale * sums (0: 1)
 };
 int disc_gather_blocks(int mb);
+size_t disc_partials_floats(int mb, int din);  // size of DiscGatherArgs::partials
 hipError_t disc_gather(const DiscGatherArgs& a, hipStream_t s);
 hipError_t disc_norm(const DiscNormArgs& a, hipStream_t s);
 hipError_t disc_adam(const DiscAdamArgs& a, hipStream_t s);

@@ -366,16 +366,22 @@ __global__ void tmlp_grad_reduce_kernel(const float* __restrict__ slab, int nblk
 
 }  // namespace
 
+// The kDisc instances carry the static disc_st[NW][kDiscStats] next to the dynamic image
+// (the plain instances have no static LDS). A two-layer net whose widest dimension pads
+// to 128 has a 4-wave image of exactly 160 KiB: with the static bytes it no longer fits.
+constexpr int kDiscStaticLds4 = 4 * kDiscStats * (int)sizeof(float);
+
 int tmlp_disc_blocks(const MLPDesc& d, int B) {
-  const TmlpPlan p = plan_tmlp(d, tmlp_waves_for(d));
+  const TmlpPlan p = plan_tmlp(d, tmlp_waves_for(d, kDiscStaticLds4));
   return (B + p.rows - 1) / p.rows;
 }
 
 hipError_t tmlp_disc_fwd_bwd(const MLPDesc& d, const float* X, int B, const DiscLoss& dl, float* slab, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (d.dims[d.n_layers] != 1 || d.out_act != ACT_IDENTITY) return hipErrorInvalidValue;
-  const int nw = tmlp_waves_for(d);
+  const int nw = tmlp_waves_for(d, kDiscStaticLds4);
   TmlpPlan p = plan_tmlp(d, nw);
+  if (p.bwd_lds + nw * kDiscStats * (int)sizeof(float) > 160 * 1024) return hipErrorInvalidValue;
   const int nblk = (B + p.rows - 1) / p.rows;
   const MLPGrads g{};
   if (nw == 4)
@@ -387,9 +393,9 @@ hipError_t tmlp_disc_fwd_bwd(const MLPDesc& d, const float* X, int B, const Disc
   return hipGetLastError();
 }
 
-int tmlp_waves_for(const MLPDesc& d) {
+int tmlp_waves_for(const MLPDesc& d, int static_lds) {
   TmlpPlan p4 = plan_tmlp(d, 4);
-  return p4.bwd_lds <= 160 * 1024 ? 4 : 2;
+  return p4.bwd_lds + static_lds <= 160 * 1024 ? 4 : 2;
 }
 
 size_t tmlp_slab_floats(const MLPDesc& d, int B) {
