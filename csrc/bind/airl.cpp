@@ -136,7 +136,7 @@ class AirlDiscPlan {
     need("Done", n);
     a_.gather_blocks = ia::airl_gather_blocks(mb_);
     a_.partials = fptr("partials");
-    need("partials", (int64_t)a_.gather_blocks * 2 * ncol);
+    need("partials", (int64_t)ia::airl_partials_floats(mb_, ncol));
     auto sums = keep(d, "sums", true);
     if (sums.defined()) {
       TORCH_CHECK(sums.scalar_type() == torch::kFloat64 && sums.numel() >= 2 * ncol, "sums: float64 [2 * cols]");
@@ -151,7 +151,8 @@ class AirlDiscPlan {
     need("stats_slab", (int64_t)n_mb_ * fb_blocks_ * ia::kDiscStats);
     a_.scale = (float)((double)mb_ / (double)B_ / (double)(2 * mb_));
     TORCH_CHECK(ia::airl_plan(a_, plan_), "AIRL discriminator outside the fused kernel's limits (widths <= 64, <= 4 "
-                                          "layers, <= 16 actions, din + 2 obs <= 128)");
+                                          "layers, <= 16 actions, din + 2 obs <= 128, LDS images <= 152 KiB: ",
+                plan_.lds_bytes, " bytes; see airl_plan_lds_bytes)");
     // Adam (disc.hip)
     ad_ = ia::DiscAdamArgs{};
     ad_.n_params = a_.n_params;
@@ -353,6 +354,27 @@ py::tuple airl_plan_sizes(int minibatch) {
   return py::make_tuple(ia::airl_gather_blocks(minibatch), ia::airl_fwd_blocks(minibatch));
 }
 
+// The fwd/bwd kernel's dynamic LDS for these layer widths (each list: input width, hidden
+// widths, output width; the policy's output is the action head), or -1 where the plan refuses
+// them: a width over 64, more than 4 layers, more than 16 actions, din_b + 2 obs_dim > 128, or an
+// image over the LDS limit. No GPU needed: what the constructor checks, for the caller to ask first.
+int airl_plan_lds_bytes(std::vector<int> pol, std::vector<int> base, std::vector<int> pot) {
+  ia::AirlDiscArgs a{};
+  auto fill = [](ia::AirlNet& n, const std::vector<int>& dims) {
+    n.n_layers = (int)dims.size() - 1;
+    if (n.n_layers < 1 || n.n_layers > ia::kAirlMaxLayers) return false;
+    for (size_t l = 0; l < dims.size(); ++l) n.dims[l] = dims[l];
+    return true;
+  };
+  if (!fill(a.pol, pol) || !fill(a.base, base) || !fill(a.pot, pot)) return -1;
+  a.D = pot[0];
+  a.A = pol.back();
+  a.din_b = base[0];
+  if (pol[0] != a.D) return -1;
+  ia::AirlPlan p{};
+  return ia::airl_plan(a, p) ? p.lds_bytes : -1;
+}
+
 }  // namespace
 
 void register_airl(py::module& m) {
@@ -381,4 +403,5 @@ void register_airl(py::module& m) {
       .def("update", &AirlDiscPlan::update, py::arg("e_idx"), py::arg("g_idx"), py::arg("step_size"), py::arg("bc2_sqrt"),
            py::arg("merge_b"), py::arg("merge_p"), py::arg("merge_q"), py::arg("stats_out") = py::none());
   m.def("airl_plan_sizes", &airl_plan_sizes, py::arg("minibatch"));
+  m.def("airl_plan_lds_bytes", &airl_plan_lds_bytes, py::arg("pol"), py::arg("base"), py::arg("pot"));
 }

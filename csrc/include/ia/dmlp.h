@@ -68,7 +68,9 @@ __device__ inline float act_apply(int act, float x) { return apply_act(act, x); 
 // Hs / Wf (and Wt / dZ / dZT below): anything indexable by layer -- pointer arrays, or
 // accessors that compute the image address (pref_rm.hip: a run-time-indexed array of LDS
 // pointers would live in scratch).
-template <class HA, class WA>
+// kLayerLd: image l has its own row stride ld_for_k(dims[l]) (airl_disc.hip packs its images
+// by width); otherwise every image has stride ld.
+template <bool kLayerLd = false, class HA, class WA>
 __device__ inline void mlp_forward(const AirlNet& net, const HA& Hs, int ld, const WA& Wf, lfl* out, int out_ld) {
   const int w = wave_id();
   for (int l = 0; l < net.n_layers; ++l) {
@@ -77,9 +79,10 @@ __device__ inline void mlp_forward(const AirlNet& net, const HA& Hs, int ld, con
     const int K = pad32(din), ldw = ld_for_k(din);
     const bool last = l == net.n_layers - 1;
     const int ntiles = last ? 1 : pad32(dout) / 16;
-    const lbf* A = Hs[l] + w * 16 * ld;
+    const int ld_in = kLayerLd ? ld_for_k(din) : ld, ld_out = kLayerLd ? ld_for_k(dout) : ld;
+    const lbf* A = Hs[l] + w * 16 * ld_in;
     for (int nt = 0; nt < ntiles; ++nt) {
-      f32x4 acc = mma_16x16(A, ld, Wimg + nt * 16 * ldw, ldw, K, zero4());
+      f32x4 acc = mma_16x16(A, ld_in, Wimg + nt * 16 * ldw, ldw, K, zero4());
       const int col = nt * 16 + acc_col();
       const float bv = col < dout ? net.b[l][col] : 0.f;
 #pragma unroll
@@ -88,7 +91,7 @@ __device__ inline void mlp_forward(const AirlNet& net, const HA& Hs, int ld, con
         if (last) {
           if (col < dout) out[r * out_ld + col] = acc[i] + bv;
         } else {
-          Hs[l + 1][r * ld + col] = to_bf16(col < dout ? act_apply(net.hidden_act, acc[i] + bv) : 0.f);
+          Hs[l + 1][r * ld_out + col] = to_bf16(col < dout ? act_apply(net.hidden_act, acc[i] + bv) : 0.f);
         }
       }
     }
@@ -104,7 +107,8 @@ __device__ inline float wave_colsum(float s) {
 // Backward of an MLP (identity output, dout = 1) from per-row output gradients dy[64]:
 // dW / db into slab[param offsets] (acc: add to what an earlier pass of this block wrote).
 // Scratch: HT [feature][row] (ld_ht), dZ [row][k] (ld) and dZT [k][row] (ld_ht), x2.
-template <class HA, class WA, class ZA>
+// kLayerLd: as mlp_forward (the dZ images keep stride ld).
+template <bool kLayerLd = false, class HA, class WA, class ZA>
 __device__ inline void mlp_backward(const AirlNet& net, const HA& Hs, int ld, const WA& Wt, const lfl* dy, lbf* HT, int ld_ht,
                              const ZA& dZ, const ZA& dZT, lfl* dbs, int dmax_pad, float* slab, bool acc_mode) {
   const int w = wave_id(), lane = lane_id();
@@ -126,12 +130,13 @@ __device__ inline void mlp_backward(const AirlNet& net, const HA& Hs, int ld, co
   bool head = true;
   for (int l = L - 1; l >= 0; --l) {
     const int din = net.dims[l], dout = net.dims[l + 1];
+    const int ld_in = kLayerLd ? ld_for_k(din) : ld;
     __syncthreads();
     {  // H^T image of this layer's input
       const int C = pad32(din);
       for (int e = threadIdx.x; e < C * kRows; e += blockDim.x) {
         const int i = e / kRows, r = e - i * kRows;
-        HT[i * ld_ht + r] = Hs[l][r * ld + i];
+        HT[i * ld_ht + r] = Hs[l][r * ld_in + i];
       }
     }
     __syncthreads();
@@ -181,7 +186,7 @@ __device__ inline void mlp_backward(const AirlNet& net, const HA& Hs, int ld, co
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = w * 16 + acc_row(i);
-          const float h = from_bf16(Hs[l][r * ld + col]);
+          const float h = from_bf16(Hs[l][r * ld_in + col]);
           const float dzval = col < din ? accv[i] * act_grad_from_out(net.hidden_act, h) : 0.f;
           dzv[i] = dzval;
           colsum += dzval;

@@ -26,6 +26,12 @@
 //                   and of both potential passes -> one gradient slab row per block
 //   disc_adam       (disc.hip) fixed-order slab reduction + torch Adam on the flat params
 //
+// airl_fwd_bwd keeps its bf16 row images (one per layer input of the base and of both potential
+// passes, each at its own width) and its weight images in LDS. Where everything fits, every
+// weight image is staged once up front; where it does not (two hidden layers of 64 in both
+// reward nets, four layers per net), one pass's weight images at a time share one region and
+// are restaged between passes (airl_plan, AirlPlan::stream_w).
+//
 // Matrix work is v_mfma_f32_16x16x32_bf16 (bf16 operands, fp32 accumulation), as in the
 // GAIL discriminator (tmlp.hip); every reduction has a fixed order, so replicas are
 // bitwise reproducible.
@@ -41,6 +47,10 @@ namespace {
 using namespace dmlp;  // kRows / kNW, staging, MLP forward / backward (ia/dmlp.h)
 constexpr int kGatherRows = 16;  // 8 rows per thread: >= 256 blocks for a 2 x 2048-row batch
 constexpr int kNormPhases = 8;
+// Dynamic LDS the fwd/bwd launch may ask for: a CU's 160 KiB less 8 KiB for the kernel's static
+// arrays (fl, heads, st_w: 6016 bytes).
+constexpr int kAirlLdsLimit = 152 * 1024;
+constexpr int kMomentSums = 4;  // per block and column: S1, S2 under two shifts (airl_gather_kernel)
 
 // ------------------------------------------------------------------ gather
 __device__ __forceinline__ float act_val(const AirlDiscArgs& a, bool expert, int64_t src, int j) {
@@ -69,9 +79,24 @@ __device__ __forceinline__ float base_col(const AirlDiscArgs& a, bool expert, in
   return (expert ? a.e_dones : a.g_dones)[src] ? 1.f : 0.f;
 }
 
+// Shift of the moment sums. The batch variance is formed as S2/n - (S1/n)^2 from fp32 block sums
+// of (v - shift) and (v - shift)^2, which is only accurate when |mean - shift| is not large
+// against the column's spread (a column at 100 +- 1 summed with shift 0 loses three digits of
+// its variance). The running mean is such a shift once it has seen data, but it is 0 on the
+// first update and absent without a normaliser. So, as disc_gather_kernel (disc.hip), every
+// block keeps two pairs of sums: one shifted by the running mean (or 0), one shifted by the
+// minibatch's own first gathered row, which each block re-gathers and airl_norm reads back from
+// row 0 of Xb / S2 / S. airl_norm takes the running-mean pair unless the two variances disagree
+// (see there), so well-centred data gives the bits it always gave.
+// The DP modes all-reduce the sums over ranks and need a shift every rank agrees on: they use
+// the running-mean pair alone. Remaining limitation: there, until the running mean has seen
+// data -- or always, without that normaliser -- an off-centre column's variance keeps that
+// cancellation error.
+//
 // statistics columns: [0, din_b) base input, [din_b, din_b + D) s', [din_b + D, din_b + 2D) s
+// partials[blk] = [S1, S2 (running-mean shift), S1, S2 (row-0 shift)][ncol]
 __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k) {
-  __shared__ float red[2][2][128];
+  __shared__ float red[2][kMomentSums][128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
   const int n = 2 * a.mb, D = a.D, nb = a.din_b;
   const int ncol = nb + 2 * D;
@@ -79,12 +104,18 @@ __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k)
   const int64_t* e_idx = a.e_idx + (size_t)k * a.mb;
   const int64_t* g_idx = a.g_idx + (size_t)k * a.mb;
   const bool col_ok = c < ncol;
-  float shift = 0.f;
+  float shift = 0.f, shift0 = 0.f;
   if (col_ok) {
-    if (c < nb) shift = a.b_mean ? a.b_mean[c] : 0.f;
-    else shift = a.p_mean ? a.p_mean[(c - nb) % D] : 0.f;
+    const int64_t src0 = e_idx[0];  // row 0 of the minibatch is its first expert row
+    if (c < nb) {
+      shift = a.b_mean ? a.b_mean[c] : 0.f;
+      shift0 = base_col(a, true, src0, c);
+    } else {
+      shift = a.p_mean ? a.p_mean[(c - nb) % D] : 0.f;
+      shift0 = c < nb + D ? a.e_next_obs[src0 * D + (c - nb)] : a.e_obs[src0 * D + (c - nb - D)];
+    }
   }
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f, s2 = 0.f, d1 = 0.f, d2 = 0.f;
 #pragma unroll
   for (int rr = ph; rr < kGatherRows; rr += 2) {
     const int r = r0 + rr;
@@ -106,6 +137,9 @@ __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k)
       const float dv = v - shift;
       s1 += dv;
       s2 += dv * dv;
+      const float dv0 = v - shift0;
+      d1 += dv0;
+      d2 += dv0 * dv0;
     }
     // raw actions for log pi (Gaussian values / categorical index) and dones (each row is
     // handled by one phase)
@@ -119,11 +153,13 @@ __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k)
   }
   red[ph][0][c] = s1;
   red[ph][1][c] = s2;
+  red[ph][2][c] = d1;
+  red[ph][3][c] = d2;
   __syncthreads();
   if (ph == 0 && col_ok) {
-    float* out = a.partials + (size_t)blockIdx.x * 2 * ncol;
-    out[c] = red[0][0][c] + red[1][0][c];
-    out[ncol + c] = red[0][1][c] + red[1][1][c];
+    float* out = a.partials + (size_t)blockIdx.x * kMomentSums * ncol;
+#pragma unroll
+    for (int q = 0; q < kMomentSums; ++q) out[q * ncol + c] = red[0][q][c] + red[1][q][c];
   }
 }
 
@@ -133,48 +169,87 @@ __device__ __forceinline__ void put_nrm(float* nrm, int slot, int c, const float
   nrm[slot * 256 + 128 + c] = mean ? rsqrtf(var[c] + eps) : 1.f;
 }
 
+// Phase ph's sums of the first NS partial rows of blocks ph, ph + 8, ... for one column, added
+// in block order; the loads of four blocks are issued together (the loop is latency-bound).
+template <int NS>
+__device__ __forceinline__ void sum_partials(const float* __restrict__ p, int ph, int nblk, int ncol,
+                                             double (&s)[kMomentSums]) {
+  constexpr int U = 4;
+  const size_t step = (size_t)kNormPhases * kMomentSums * ncol;
+  int b = ph;
+  for (; b + (U - 1) * kNormPhases < nblk; b += U * kNormPhases, p += U * step) {
+    float v[U][NS];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int q = 0; q < NS; ++q) v[u][q] = p[u * step + (size_t)q * ncol];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int q = 0; q < NS; ++q) s[q] += (double)v[u][q];
+  }
+  for (; b < nblk; b += kNormPhases, p += step)
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] += (double)p[(size_t)q * ncol];
+}
+
+// The two variances of a column (see airl_gather_kernel) agree to rounding when the running
+// mean is a fair centre of the batch; then the running-mean pair is used, as it always was.
+// Where they differ by more than kMomentRtol of the row-0 variance, the running-mean pair has
+// lost that much to cancellation and the row-0 pair, whose error stays near fp32 rounding
+// whatever the column's offset, is used instead (the threshold of disc_norm_kernel).
+constexpr double kMomentRtol = 1e-5;
+
 // 1024 threads = 8 block-phases x 128 columns (fixed-order reduction, as disc_norm_kernel)
 __global__ __launch_bounds__(128 * kNormPhases) void airl_norm_kernel(AirlDiscArgs a, int mode, int n_total) {
-  __shared__ double red[kNormPhases][2][128];
+  __shared__ double red[kNormPhases][kMomentSums][128];
   __shared__ float bm[128], bv[128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
   const int D = a.D, nb = a.din_b, ncol = nb + 2 * D;
   const int n = mode == 2 ? n_total : 2 * a.mb;
   if (mode != 2) {
-    double s1 = 0.0, s2 = 0.0;
-    if (c < ncol)
-      for (int b = ph; b < a.gather_blocks; b += kNormPhases) {
-        const float* p = a.partials + (size_t)b * 2 * ncol;
-        s1 += (double)p[c];
-        s2 += (double)p[ncol + c];
-      }
-    red[ph][0][c] = s1;
-    red[ph][1][c] = s2;
+    double s[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
+    if (c < ncol) {
+      const float* p = a.partials + (size_t)ph * kMomentSums * ncol + c;
+      if (mode == 0) sum_partials<kMomentSums>(p, ph, a.gather_blocks, ncol, s);
+      else sum_partials<2>(p, ph, a.gather_blocks, ncol, s);  // the DP sums carry the shared shift only
+    }
+#pragma unroll
+    for (int q = 0; q < kMomentSums; ++q) red[ph][q][c] = s[q];
     __syncthreads();
   }
   if (ph == 0 && c < ncol) {
-    double S1 = 0.0, S2 = 0.0;
+    double S[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
     if (mode == 2) {
-      S1 = a.sums[c];
-      S2 = a.sums[ncol + c];
+      S[0] = a.sums[c];
+      S[1] = a.sums[ncol + c];
     } else {
-      for (int q = 0; q < kNormPhases; ++q) {
-        S1 += red[q][0][c];
-        S2 += red[q][1][c];
-      }
+      for (int q = 0; q < kNormPhases; ++q)
+#pragma unroll
+        for (int j = 0; j < kMomentSums; ++j) S[j] += red[q][j][c];
     }
     if (mode == 1) {
-      a.sums[c] = S1;
-      a.sums[ncol + c] = S2;
+      a.sums[c] = S[0];
+      a.sums[ncol + c] = S[1];
     } else {
       float shift = 0.f;
       if (c < nb) shift = a.b_mean ? a.b_mean[c] : 0.f;
       else shift = a.p_mean ? a.p_mean[(c - nb) % D] : 0.f;
-      const double m = S1 / n;
-      double var = S2 / n - m * m;
+      const double m = S[0] / n;
+      double var = S[1] / n - m * m;
       if (var < 0.0) var = 0.0;
       bm[c] = (float)((double)shift + m);
       bv[c] = (float)var;
+      if (mode == 0) {
+        const double m0 = S[2] / n;
+        double var0 = S[3] / n - m0 * m0;
+        if (var0 < 0.0) var0 = 0.0;
+        if (fabs(var - var0) > kMomentRtol * var0) {
+          const float row0 = c < nb ? a.Xb[c] : c < nb + D ? a.S2[c - nb] : a.S[c - nb - D];
+          bm[c] = (float)((double)row0 + m0);
+          bv[c] = (float)var0;
+        }
+      }
     }
   }
   if (mode == 1) return;
@@ -250,9 +325,9 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
   {
     const int nb = a.base.n_layers, np = a.pot.n_layers;
     for (int l = 0; l < kAirlMaxLayers; ++l) {
-      Bh[l] = (lbf*)(smem + p.rimg_off + (size_t)min(l, nb - 1) * p.rimg_bytes);
-      Qh[l] = (lbf*)(smem + p.rimg_off + (size_t)(nb + min(l, np - 1)) * p.rimg_bytes);
-      Rh[l] = (lbf*)(smem + p.rimg_off + (size_t)(nb + np + min(l, np - 1)) * p.rimg_bytes);
+      Bh[l] = (lbf*)(smem + p.img_off[0][min(l, nb - 1)]);
+      Qh[l] = (lbf*)(smem + p.img_off[1][min(l, np - 1)]);
+      Rh[l] = (lbf*)(smem + p.img_off[2][min(l, np - 1)]);
     }
   }
   // backward scratch aliases the policy images (the policy pass is over by then)
@@ -271,19 +346,31 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
   lds_zero(smem, p.lds_bytes);
   __syncthreads();
   // every weight image once, up front (forward [o][i]; transposed [i][o] for the backward of
-  // the reward nets' layers >= 1), all loads in flight together
-  {
-    const AirlNet* nets[3] = {&a.pol, &a.base, &a.pot};
-    for (int q = 0; q < 3; ++q)
-      for (int l = 0; l < nets[q]->n_layers; ++l) {
-        stage_weights(Wf[q][l], nets[q]->W[l], nets[q]->dims[l + 1], nets[q]->dims[l], false);
-        if (q > 0 && l > 0) stage_weights(Wt[q][l], nets[q]->W[l], nets[q]->dims[l + 1], nets[q]->dims[l], true);
-      }
+  // the reward nets' layers >= 1), all loads in flight together; or (p.stream_w) the images of
+  // one pass at a time into a shared region, the policy's first
+  const AirlNet* nets[3] = {&a.pol, &a.base, &a.pot};
+  auto stage_net = [&](int q, bool transposed) {
+    for (int l = transposed ? 1 : 0; l < nets[q]->n_layers; ++l)
+      stage_weights(transposed ? Wt[q][l] : Wf[q][l], nets[q]->W[l], nets[q]->dims[l + 1], nets[q]->dims[l], transposed);
+  };
+  // restage between passes: every wave is done with the region's previous images first
+  auto restage = [&](int q, bool transposed) {
+    __syncthreads();
+    stage_net(q, transposed);
+    __syncthreads();
+  };
+  if (p.stream_w) {
+    stage_net(0, false);
+  } else {
+    for (int q = 0; q < 3; ++q) {
+      stage_net(q, false);
+      if (q > 0) stage_net(q, true);
+    }
   }
   stage_rows(Pimg[0], p.ldp, a.S, a.D, n, row0, a.nrm + 0 * 256);
-  stage_rows(Bh[0], p.ldr, a.Xb, a.din_b, n, row0, a.nrm + 1 * 256);
-  stage_rows(Qh[0], p.ldr, a.S2, a.D, n, row0, a.nrm + 2 * 256);
-  stage_rows(Rh[0], p.ldr, a.S, a.D, n, row0, a.nrm + 3 * 256);
+  stage_rows(Bh[0], ld_for_k(a.din_b), a.Xb, a.din_b, n, row0, a.nrm + 1 * 256);
+  stage_rows(Qh[0], ld_for_k(a.D), a.S2, a.D, n, row0, a.nrm + 2 * 256);
+  stage_rows(Rh[0], ld_for_k(a.D), a.S, a.D, n, row0, a.nrm + 3 * 256);
   __syncthreads();
 
   unsigned long long t_1 = stamp ? clock64() : 0;
@@ -338,9 +425,11 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
 
   unsigned long long t_2 = stamp ? clock64() : 0;
   // ---- reward nets forward: base r, potential Phi(s'), Phi(s)
-  mlp_forward(a.base, Bh, p.ldr, Wf[1], (lfl*)&fl[1][0], 1);
-  mlp_forward(a.pot, Qh, p.ldr, Wf[2], (lfl*)&fl[2][0], 1);
-  mlp_forward(a.pot, Rh, p.ldr, Wf[2], (lfl*)&fl[3][0], 1);
+  if (p.stream_w) restage(1, false);
+  mlp_forward<true>(a.base, Bh, p.ldr, Wf[1], (lfl*)&fl[1][0], 1);
+  if (p.stream_w) restage(2, false);
+  mlp_forward<true>(a.pot, Qh, p.ldr, Wf[2], (lfl*)&fl[2][0], 1);
+  mlp_forward<true>(a.pot, Rh, p.ldr, Wf[2], (lfl*)&fl[3][0], 1);
   __syncthreads();
 
   unsigned long long t_3 = stamp ? clock64() : 0;
@@ -386,10 +475,12 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
   unsigned long long t_4 = stamp ? clock64() : 0;
   // ---- backward: base, potential on s' (writes), potential on s (adds)
   float* slab_row = a.slab + ((size_t)k * gridDim.x + blockIdx.x) * a.n_params;
-  mlp_backward(a.base, Bh, p.ldr, Wt[1], (const lfl*)&fl[4][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, false);
-  mlp_backward(a.pot, Qh, p.ldr, Wt[2], (const lfl*)&fl[5][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, false);
+  if (p.stream_w) restage(1, true);
+  mlp_backward<true>(a.base, Bh, p.ldr, Wt[1], (const lfl*)&fl[4][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, false);
+  if (p.stream_w) restage(2, true);
+  mlp_backward<true>(a.pot, Qh, p.ldr, Wt[2], (const lfl*)&fl[5][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, false);
   unsigned long long t_5 = stamp ? clock64() : 0;
-  mlp_backward(a.pot, Rh, p.ldr, Wt[2], (const lfl*)&fl[1][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, true);
+  mlp_backward<true>(a.pot, Rh, p.ldr, Wt[2], (const lfl*)&fl[1][0], HT, p.ld_ht, dZ, dZT, dbs, p.dmax_pad, slab_row, true);
   if (stamp) {
     const unsigned long long t_6 = clock64();
     a.prof[0] += t_1 - t_0;  // zero + stage
@@ -406,6 +497,7 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
 
 int airl_gather_blocks(int mb) { return (2 * mb + kGatherRows - 1) / kGatherRows; }
 int airl_fwd_blocks(int mb) { return (2 * mb + kRows - 1) / kRows; }
+size_t airl_partials_floats(int mb, int ncol) { return (size_t)airl_gather_blocks(mb) * kMomentSums * ncol; }
 
 bool airl_plan(const AirlDiscArgs& a, AirlPlan& p) {
   p = AirlPlan{};
@@ -433,28 +525,66 @@ bool airl_plan(const AirlDiscArgs& a, AirlPlan& p) {
   p.ht_bytes = pad32(rmax) * p.ld_ht * 2;
   if (p.ht_bytes < kRows * 32 * 2) p.ht_bytes = kRows * 32 * 2;
   (void)wmax;
-  int off = 0;
-  for (int q = 0; q < 3; ++q)
-    for (int l = 0; l < kAirlMaxLayers; ++l) {
-      p.wf_off[q][l] = p.wt_off[q][l] = 0;
-      if (l >= nets[q]->n_layers) continue;
-      const int din = nets[q]->dims[l], dout = nets[q]->dims[l + 1];
-      p.wf_off[q][l] = off;
-      off += (pad32(dout) * ld_for_k(din) * 2 + 15) & ~15;
-      if (q > 0 && l > 0) {
-        p.wt_off[q][l] = off;
-        off += (pad32(din) * ld_for_k(dout) * 2 + 15) & ~15;
-      }
-    }
-  p.rimg_off = off;
-  off += (a.base.n_layers + 2 * a.pot.n_layers) * p.rimg_bytes;
-  p.scratch_off = off;
+  auto wf_bytes = [&](int q, int l) { return (pad32(nets[q]->dims[l + 1]) * ld_for_k(nets[q]->dims[l]) * 2 + 15) & ~15; };
+  auto wt_bytes = [&](int q, int l) { return (pad32(nets[q]->dims[l]) * ld_for_k(nets[q]->dims[l + 1]) * 2 + 15) & ~15; };
+  // row images, packed by width: the inputs of every layer of the base and of both potential passes
+  int img_bytes = 0;
+  for (int l = 0; l < a.base.n_layers; ++l) img_bytes += kRows * ld_for_k(a.base.dims[l]) * 2;
+  for (int l = 0; l < a.pot.n_layers; ++l) img_bytes += 2 * kRows * ld_for_k(a.pot.dims[l]) * 2;
   const int pol_scratch = 2 * p.pimg_bytes;
   const int bwd_scratch = 3 * p.ht_bytes + 2 * p.rimg_bytes + (2 * kNW * p.dmax_pad + 16) * 4;
   // dZT images are [k][row] with k < 32 here (pad32(dout) of the backward operand <= pad32(rmax))
-  off += ((pol_scratch > bwd_scratch ? pol_scratch : bwd_scratch) + 15) & ~15;
+  const int scratch_bytes = ((pol_scratch > bwd_scratch ? pol_scratch : bwd_scratch) + 15) & ~15;
+  // weight images: all resident where that fits, else one pass's images at a time in one region
+  int set_bytes[5] = {0, 0, 0, 0, 0};  // policy fwd, base fwd, potential fwd, base bwd, potential bwd
+  for (int q = 0; q < 3; ++q)
+    for (int l = 0; l < nets[q]->n_layers; ++l) {
+      set_bytes[q] += wf_bytes(q, l);
+      if (q > 0 && l > 0) set_bytes[2 + q] += wt_bytes(q, l);
+    }
+  int resident = 0, region = 0;
+  for (int i = 0; i < 5; ++i) {
+    resident += set_bytes[i];
+    region = region > set_bytes[i] ? region : set_bytes[i];
+  }
+  p.stream_w = resident + img_bytes + scratch_bytes > kAirlLdsLimit ? 1 : 0;
+  int off = 0;
+  for (int q = 0; q < 3; ++q) {
+    int fwd = 0, bwd = 0;  // offsets within a pass's set (stream_w)
+    for (int l = 0; l < kAirlMaxLayers; ++l) {
+      p.wf_off[q][l] = p.wt_off[q][l] = 0;
+      if (l >= nets[q]->n_layers) continue;
+      if (p.stream_w) {
+        p.wf_off[q][l] = fwd;
+        fwd += wf_bytes(q, l);
+        if (q > 0 && l > 0) {
+          p.wt_off[q][l] = bwd;
+          bwd += wt_bytes(q, l);
+        }
+      } else {  // the layout this plan always had
+        p.wf_off[q][l] = off;
+        off += wf_bytes(q, l);
+        if (q > 0 && l > 0) {
+          p.wt_off[q][l] = off;
+          off += wt_bytes(q, l);
+        }
+      }
+    }
+  }
+  if (p.stream_w) off = region;
+  for (int i = 0; i < 3; ++i) {
+    const AirlNet& n = i == 0 ? a.base : a.pot;
+    for (int l = 0; l < kAirlMaxLayers; ++l) {
+      p.img_off[i][l] = 0;
+      if (l >= n.n_layers) continue;
+      p.img_off[i][l] = off;
+      off += kRows * ld_for_k(n.dims[l]) * 2;
+    }
+  }
+  p.scratch_off = off;
+  off += scratch_bytes;
   p.lds_bytes = off;
-  return p.lds_bytes <= 144 * 1024;
+  return p.lds_bytes <= kAirlLdsLimit;
 }
 
 hipError_t airl_gather(const AirlDiscArgs& a, int k, hipStream_t s) {

@@ -137,12 +137,18 @@ struct AirlDiscArgs {
 struct AirlPlan {
   int ldp, ldr, ld_ht, dmax_pad;
   int pimg_bytes, rimg_bytes, ht_bytes;
-  int wf_off[3][kAirlMaxLayers];  // pre-staged weight images: 0 policy, 1 base, 2 potential
+  int wf_off[3][kAirlMaxLayers];  // weight images: 0 policy, 1 base, 2 potential
   int wt_off[3][kAirlMaxLayers];  // transposed images (reward nets, layers >= 1)
-  int rimg_off, scratch_off, lds_bytes;
+  // 0: every weight image resident, staged once up front. 1: the images of one pass at a time
+  // share one region (policy fwd, base fwd, potential fwd, base bwd, potential bwd), restaged
+  // between passes: taken only where the resident layout is over the LDS limit
+  int stream_w;
+  int img_off[3][kAirlMaxLayers];  // row images [64][ld_for_k(width)]: 0 base, 1 potential on s', 2 potential on s
+  int scratch_off, lds_bytes;
 };
 int airl_gather_blocks(int mb);
 int airl_fwd_blocks(int mb);
+size_t airl_partials_floats(int mb, int ncol);  // size of AirlDiscArgs::partials (ncol = din_b + 2 D)
 bool airl_plan(const AirlDiscArgs& a, AirlPlan& p);
 hipError_t airl_gather(const AirlDiscArgs& a, int k, hipStream_t s);
 hipError_t airl_norm(const AirlDiscArgs& a, int mode, int n_total, hipStream_t s);

@@ -134,6 +134,11 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         din = (base.use_state + base.use_next_state) * self.D + base.use_action * self.A + base.use_done
         if din + 2 * self.D > 128:
             return False, "too many input columns"
+        # every weight and row image of the three nets is resident in LDS at once: deep or wide
+        # combinations inside the limits above can still be over it
+        dims = [[l.in_features for l in lins] + [lins[-1].out_features] for lins in (qlins, blins, plins)]
+        if self._C.airl_plan_lds_bytes(*dims) < 0:
+            return False, "MLP images over the fused kernel's LDS limit"
         return True, ""
 
     def _setup_fused_disc(self) -> None:
@@ -180,7 +185,7 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         z = lambda *sh, dt=th.float32: th.zeros(*sh, device=dev, dtype=dt)  # noqa: E731
         rows = 2 * mb
         self._disc_ws = dict(Xb=z(rows * din), S=z(rows * D), S2=z(rows * D), Act=z(rows * (1 if self.discrete else self.A)),
-                             Done=z(rows), partials=z(gblk * 2 * ncol), sums=z(2 * ncol, dt=th.float64), nrm=z(4 * 256),
+                             Done=z(rows), partials=z(gblk * 4 * ncol), sums=z(2 * ncol, dt=th.float64), nrm=z(4 * 256),
                              slab=z((B // mb) * fblk * n), stats_slab=z((B // mb) * fblk * 8), grads=z(n))
         self._disc_stats = z(max(1, self.n_disc_updates_per_round), 8)
         g = self._disc_opt.param_groups[0]
