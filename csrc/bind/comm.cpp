@@ -5,12 +5,6 @@
 
 namespace {
 
-#define IA_HIP_CHECK(expr)                                                            \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 py::tuple oneshot_alloc(int64_t stage_bytes) {
   TORCH_CHECK(stage_bytes > 0 && stage_bytes % 16 == 0, "stage_bytes must be a positive multiple of 16");
   void* p = nullptr;

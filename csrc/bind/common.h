@@ -14,6 +14,11 @@ namespace py = pybind11;
   IA_CHECK_CUDA(t);         \
   IA_CHECK_CONTIG(t);       \
   IA_CHECK_F32(t)
+#define IA_HIP_CHECK(expr)                                                            \
+  do {                                                                                \
+    hipError_t _e = (expr);                                                           \
+    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
+  } while (0)
 
 inline hipStream_t ia_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 

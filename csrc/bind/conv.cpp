@@ -4,12 +4,6 @@
 
 namespace {
 
-#define IA_HIP_CHECK3(expr)                                                           \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 int in_kind(const torch::Tensor& x) {
   switch (x.scalar_type()) {
     case torch::kFloat32: return 0;
@@ -68,11 +62,11 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wb, c10::optional<torch::T
   }
   auto y = torch::empty({g.B, g.OH, g.OW, g.N}, x.options().dtype(torch::kBFloat16));
   if (splitk && ia::conv_forward_sk_ok(g)) {  // (else the default form)
-    IA_HIP_CHECK3(ia::conv_forward_sk(in_kind(x), x.data_ptr(), wk.data_ptr(), b, y.data_ptr(), g, (float)in_scale,
+    IA_HIP_CHECK(ia::conv_forward_sk(in_kind(x), x.data_ptr(), wk.data_ptr(), b, y.data_ptr(), g, (float)in_scale,
                                       relu ? 1 : 0, ia_stream()));
     return y;
   }
-  IA_HIP_CHECK3(ia::conv_forward(in_kind(x), x.data_ptr(), wk.data_ptr(), b, y.data_ptr(), g, (float)in_scale, relu ? 1 : 0,
+  IA_HIP_CHECK(ia::conv_forward(in_kind(x), x.data_ptr(), wk.data_ptr(), b, y.data_ptr(), g, (float)in_scale, relu ? 1 : 0,
                                  ia_stream()));
   return y;
 }
@@ -94,7 +88,7 @@ torch::Tensor conv_wgrad_partials(torch::Tensor x, torch::Tensor dy, torch::Tens
     TORCH_CHECK(y.sizes() == dy.sizes() && y.scalar_type() == torch::kBFloat16, "y must match dy");
   }
   auto slab = torch::empty({(int64_t)ia::conv_wgrad_slab_floats(g)}, x.options().dtype(torch::kFloat32));
-  IA_HIP_CHECK3(ia::conv_wgrad(in_kind(x), x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr,
+  IA_HIP_CHECK(ia::conv_wgrad(in_kind(x), x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr,
                                slab.data_ptr<float>(), nullptr, nullptr, g, (float)in_scale, relu_out ? 1 : 0, ia_stream()));
   return slab;
 }
@@ -136,7 +130,7 @@ void conv_reduce_multi(std::vector<torch::Tensor> xs, std::vector<torch::Tensor>
                        std::vector<int64_t> KWs, std::vector<int64_t> strides, std::vector<int64_t> pads,
                        std::vector<torch::Tensor> slabs, std::vector<torch::Tensor> dWs, std::vector<torch::Tensor> dbs) {
   const ia::ConvReduceMulti r = conv_reduce_args(xs, dys, KHs, KWs, strides, pads, slabs, dWs, dbs);
-  IA_HIP_CHECK3(ia::conv_reduce_multi(r, ia_stream()));
+  IA_HIP_CHECK(ia::conv_reduce_multi(r, ia_stream()));
 }
 
 py::tuple conv_wgrad(torch::Tensor x, torch::Tensor dy, torch::Tensor y, int64_t KH, int64_t KW, int64_t stride,
@@ -175,7 +169,7 @@ py::tuple conv_wgrad(torch::Tensor x, torch::Tensor dy, torch::Tensor y, int64_t
   } else {
     db = torch::empty({g.N}, f32);
   }
-  IA_HIP_CHECK3(ia::conv_wgrad(in_kind(x), x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr,
+  IA_HIP_CHECK(ia::conv_wgrad(in_kind(x), x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr,
                                slab.data_ptr<float>(), dW.data_ptr<float>(), db.data_ptr<float>(), g, (float)in_scale,
                                relu_out ? 1 : 0, ia_stream()));
   return py::make_tuple(dW, db);
@@ -202,7 +196,7 @@ torch::Tensor conv_dgrad(torch::Tensor dy, torch::Tensor y, torch::Tensor wt, to
     TORCH_CHECK(y.sizes() == dy.sizes() && y.scalar_type() == torch::kBFloat16, "y must match dy");
   }
   auto dz = torch::empty({g.B, g.H, g.W, g.C}, xp.options());
-  IA_HIP_CHECK3(ia::conv_dgrad(dy.data_ptr(), relu_out ? y.data_ptr() : nullptr, wt.data_ptr(), xp.data_ptr(),
+  IA_HIP_CHECK(ia::conv_dgrad(dy.data_ptr(), relu_out ? y.data_ptr() : nullptr, wt.data_ptr(), xp.data_ptr(),
                                dz.data_ptr(), g, relu_out ? 1 : 0, relu_in ? 1 : 0, ia_stream(), (int)form));
   return dz;
 }
@@ -229,7 +223,7 @@ py::tuple conv_backward_pair(torch::Tensor x, torch::Tensor dy, torch::Tensor y,
   TORCH_CHECK(ia::conv_back_pair_ok(g), "conv_backward_pair: geometry outside the paired kernel");
   auto slab = torch::empty({(int64_t)ia::conv_wgrad_slab_floats(g)}, x.options().dtype(torch::kFloat32));
   auto dz = torch::empty({g.B, g.H, g.W, g.C}, x.options());
-  IA_HIP_CHECK3(ia::conv_back_pair(x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr, slab.data_ptr<float>(),
+  IA_HIP_CHECK(ia::conv_back_pair(x.data_ptr(), dy.data_ptr(), relu_out ? y.data_ptr() : nullptr, slab.data_ptr<float>(),
                                    wt.data_ptr(), dz.data_ptr(), g, relu_out ? 1 : 0, 1, ia_stream()));
   return py::make_tuple(slab, dz);
 }
@@ -279,7 +273,7 @@ py::tuple conv_pack_weights(std::vector<torch::Tensor> ws, std::vector<bool> wan
     wts.push_back(wt);
   }
   if (gather.is_none()) {
-    IA_HIP_CHECK3(ia::conv_pack_weights(a, ia_stream()));
+    IA_HIP_CHECK(ia::conv_pack_weights(a, ia_stream()));
   } else {
     auto g = gather.cast<py::tuple>();
     TORCH_CHECK(g.size() == 6, "conv_pack_weights: gather = (srcs, perm, cursor, n, dst, inc)");
@@ -292,7 +286,7 @@ py::tuple conv_pack_weights(std::vector<torch::Tensor> ws, std::vector<bool> wan
     if (!g[5].is_none()) inc = g[5].cast<torch::Tensor>();
     float* incp = nullptr;
     const ia::GatherArgs ga = gather_cursor_args(srcs, perm, cursor, n, dst, inc, &incp);
-    IA_HIP_CHECK3(ia::conv_pack_weights(a, ia_stream(), &ga, perm.data_ptr<int>(), cursor.data_ptr<int>(), (int)n, incp));
+    IA_HIP_CHECK(ia::conv_pack_weights(a, ia_stream(), &ga, perm.data_ptr<int>(), cursor.data_ptr<int>(), (int)n, incp));
   }
   py::list lb, lt;
   for (size_t i = 0; i < ws.size(); ++i) {
@@ -317,7 +311,7 @@ torch::Tensor cnn_fc(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
   const int NH = (int)w.size(0);
   TORCH_CHECK(b.numel() == NH && K % 32 == 0 && NH % 16 == 0, "cnn_fc: K % 32, NH % 16, bias [NH]");
   auto h = torch::empty({B, NH}, x.options().dtype(torch::kFloat32));
-  IA_HIP_CHECK3(ia::cnn_fc(x.data_ptr(), w.data_ptr(), b.data_ptr<float>(), h.data_ptr<float>(), B, (int)K, NH, ia_stream()));
+  IA_HIP_CHECK(ia::cnn_fc(x.data_ptr(), w.data_ptr(), b.data_ptr<float>(), h.data_ptr<float>(), B, (int)K, NH, ia_stream()));
   return h;
 }
 
@@ -359,7 +353,7 @@ py::tuple fc_backward(torch::Tensor x, torch::Tensor dh, torch::Tensor h, torch:
   torch::Tensor dx;
   if (need_dx) dx = torch::empty({M, K}, x.options());
   auto dzb = torch::empty({M, NH}, x.options());  // bf16 dZ, fc_wgrad -> fc_dgrad
-  IA_HIP_CHECK3(ia::fc_backward(x.data_ptr(), dhc.data_ptr<float>(), h.data_ptr<float>(), wt.data_ptr(),
+  IA_HIP_CHECK(ia::fc_backward(x.data_ptr(), dhc.data_ptr<float>(), h.data_ptr<float>(), wt.data_ptr(),
                                 dW.data_ptr<float>(), db.data_ptr<float>(), need_dx ? dx.data_ptr() : nullptr, dzb.data_ptr(), M,
                                 (int)K, NH, (int)C, (int)(K / C), ia_stream(), mask_dx));
   return py::make_tuple(dW, db, need_dx ? py::cast(dx) : py::none());
@@ -386,7 +380,7 @@ py::tuple conv_fwd_pair(torch::Tensor x1, torch::Tensor x2, torch::Tensor w1, to
   auto y2 = torch::empty_like(y1);
   ia::ConvPair p{{x1.data_ptr(), x2.data_ptr()}, {w1.data_ptr(), w2.data_ptr()}, {b1.data_ptr<float>(), b2.data_ptr<float>()},
                  {y1.data_ptr(), y2.data_ptr()}};
-  IA_HIP_CHECK3(ia::conv_fwd_pair(in_kind(x1), p, g, (float)in_scale, relu ? 1 : 0, ia_stream()));
+  IA_HIP_CHECK(ia::conv_fwd_pair(in_kind(x1), p, g, (float)in_scale, relu ? 1 : 0, ia_stream()));
   return py::make_tuple(y1, y2);
 }
 
@@ -410,7 +404,7 @@ py::tuple cnn_fc_pair(torch::Tensor x1, torch::Tensor x2, torch::Tensor w1, torc
   auto h2 = torch::empty_like(h1);
   ia::CnnFcPair p{{x1.data_ptr(), x2.data_ptr()}, {w1.data_ptr(), w2.data_ptr()}, {b1.data_ptr<float>(), b2.data_ptr<float>()},
                   {h1.data_ptr<float>(), h2.data_ptr<float>()}};
-  IA_HIP_CHECK3(ia::cnn_fc_pair(p, B, (int)K, NH, ia_stream()));
+  IA_HIP_CHECK(ia::cnn_fc_pair(p, B, (int)K, NH, ia_stream()));
   return py::make_tuple(h1, h2);
 }
 
@@ -458,7 +452,7 @@ void cnn_head(torch::Tensor h, torch::Tensor w2, torch::Tensor b2, int64_t mode,
               c10::optional<torch::Tensor> mix_expert, c10::optional<torch::Tensor> beta,
               c10::optional<torch::Tensor> exec_out) {
   const ia::CnnHeadArgs a = head_args(h, w2, b2, mode, seed, counter, out, rec_out, mix_expert, beta, exec_out);
-  IA_HIP_CHECK3(ia::cnn_head(a, ia_stream()));
+  IA_HIP_CHECK(ia::cnn_head(a, ia_stream()));
 }
 
 // DAgger's expert argmax (-> out_e, rec_out_e) and learner Gumbel sample (-> out_l, and
@@ -471,7 +465,7 @@ void cnn_head_pair(torch::Tensor h_e, torch::Tensor w_e, torch::Tensor b_e, torc
                                       c10::nullopt);
   const ia::CnnHeadArgs r = head_args(h_l, w_l, b_l, 1, seed, counter, out_l, c10::nullopt, out_e, beta, exec_out);
   TORCH_CHECK(e.B == r.B && e.NH == r.NH, "cnn_head_pair: the two heads' batch / hidden sizes differ");
-  IA_HIP_CHECK3(ia::cnn_head_pair(e, r, ia_stream()));
+  IA_HIP_CHECK(ia::cnn_head_pair(e, r, ia_stream()));
 }
 
 }  // namespace

@@ -8,12 +8,6 @@
 
 namespace {
 
-#define IA_HIP_CHECK2(expr)                                                           \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 template <typename T>
 T* tptr(const py::dict& d, const char* k, bool optional = false) {
   if (!d.contains(k) || d[k].is_none()) {
@@ -95,7 +89,7 @@ void rollout(py::dict d) {
     a.prof = reinterpret_cast<long long*>(t.data_ptr());
   }
   a.lds_actor = ival(d, "lds_actor", 0);
-  IA_HIP_CHECK2(ia::rollout_launch(a, ia_stream()));
+  IA_HIP_CHECK(ia::rollout_launch(a, ia_stream()));
 }
 
 void rollout_post(py::dict d) {
@@ -147,7 +141,7 @@ void rollout_post(py::dict d) {
   a.rewards = tptr<float>(d, "rewards");
   a.rew_raw = tptr<float>(d, "rew_raw", true);
   a.last_values = tptr<float>(d, "last_values");
-  IA_HIP_CHECK2(ia::rollout_post_launch(a, ia_stream()));
+  IA_HIP_CHECK(ia::rollout_post_launch(a, ia_stream()));
 }
 
 void reward_outnorm(py::dict d) {
@@ -164,7 +158,7 @@ void reward_outnorm(py::dict d) {
   a.count = tptr<float>(d, "count", a.count_i != nullptr);
   a.eps = (float)fval(d, "eps", 1e-5);
   a.step_stats = tptr<const float>(d, "step_stats", true);
-  IA_HIP_CHECK2(ia::reward_outnorm_launch(a, ia_stream()));
+  IA_HIP_CHECK(ia::reward_outnorm_launch(a, ia_stream()));
 }
 
 void reward_retnorm(py::dict d) {
@@ -192,7 +186,7 @@ void reward_retnorm(py::dict d) {
   a.gamma = fval(d, "gamma", 0.99);
   a.eps = fval(d, "eps", 1e-8);
   a.clip = fval(d, "clip", 10.0);
-  IA_HIP_CHECK2(ia::reward_retnorm_launch(a, ia_stream()));
+  IA_HIP_CHECK(ia::reward_retnorm_launch(a, ia_stream()));
 }
 
 // The shape and planning fields of PPOArgs (what ppo_rc_plan / ppo_lds_bytes read): the part of
@@ -283,10 +277,10 @@ void ppo_update(py::dict d) {
   if (a.mode == 0 && ival(d, "allow_rc", 1) && ia::ppo_rc_plan(a, plan)) {
     auto ws = torch::empty({(int64_t)plan.workspace_floats},
                            torch::TensorOptions().dtype(torch::kFloat32).device(torch::kCUDA, c10::hip::current_device()));
-    IA_HIP_CHECK2(ia::ppo_rc_launch(a, plan, ws.data_ptr<float>(), ia_stream()));
+    IA_HIP_CHECK(ia::ppo_rc_launch(a, plan, ws.data_ptr<float>(), ia_stream()));
     return;
   }
-  IA_HIP_CHECK2(ia::ppo_launch(a, ia_stream()));
+  IA_HIP_CHECK(ia::ppo_launch(a, ia_stream()));
 }
 
 std::string ppo_path_of(const ia::PPORcGeo& g) {
@@ -348,7 +342,7 @@ torch::Tensor ppo_image_probe(torch::Tensor x, int mode) {
               "engine_ppo_image_probe: rows and features multiples of 16, at most 64");
   TORCH_CHECK(mode == 0 || mode == 1, "engine_ppo_image_probe: mode 0 (packed store) or 1 (per element)");
   auto out = torch::zeros({2, feats / 16, (rows > 32 ? 64 : 32) / 32, 64, 8}, x.options().dtype(torch::kInt16));
-  IA_HIP_CHECK2(ia::ppo_image_probe_launch(x.data_ptr<float>(), rows, feats, mode,
+  IA_HIP_CHECK(ia::ppo_image_probe_launch(x.data_ptr<float>(), rows, feats, mode,
                                            reinterpret_cast<unsigned short*>(out.data_ptr<int16_t>()), ia_stream()));
   return out;
 }
@@ -408,7 +402,7 @@ void dagger_env_step(py::dict d) {
       check_numel("obs_rec", a.N * obs_elems);
     }
   }
-  IA_HIP_CHECK2(ia::dagger_env_step(a, ia_stream()));
+  IA_HIP_CHECK(ia::dagger_env_step(a, ia_stream()));
 }
 
 void register_engine(py::module& m) {

@@ -4,12 +4,6 @@
 
 namespace {
 
-#define IA_HIP_CHECK(expr)                                                            \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 ia::MLPDesc make_desc(const std::vector<torch::Tensor>& Ws, const std::vector<torch::Tensor>& bs, int64_t hidden_act,
                       int64_t out_act, const c10::optional<torch::Tensor>& mean, const c10::optional<torch::Tensor>& var,
                       double eps, double clip) {

@@ -3,96 +3,46 @@
 // tensors (device-resident fragment dataset, reward-net weights and RunningNorm buffers, the
 // FusedAdam flat parameters, moments and device step counter); a minibatch then passes only
 // its pair ids: one pybind call, four launches, no host sync, HIP-graph capturable.
-#include "common.h"
-#include "launchers.h"
+#include "plan_args.h"
 
 #include <algorithm>
 
 namespace {
 
-#define IA_HIP_CHECK_P(expr)                                                          \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 class PrefRmPlan {
  public:
-  explicit PrefRmPlan(py::dict d) {
-    auto keep = [&](const char* k, bool optional = false) -> torch::Tensor {
-      if (!d.contains(k) || d[k].is_none()) {
-        TORCH_CHECK(optional, "pref plan arg missing: ", k);
-        return torch::Tensor();
-      }
-      auto t = d[k].cast<torch::Tensor>();
-      TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "pref plan arg ", k, " must be a contiguous GPU tensor");
-      held_.push_back(t);
-      return t;
-    };
-    auto fptr = [&](const char* k, bool optional = false) -> float* {
-      auto t = keep(k, optional);
-      if (!t.defined()) return nullptr;
-      TORCH_CHECK(t.scalar_type() == torch::kFloat32, k, " must be float32");
-      return t.data_ptr<float>();
-    };
+  explicit PrefRmPlan(py::dict d) : pd_(d, "pref") {
     a_ = ia::PrefRmArgs{};
-    a_.L = d["L"].cast<int>();
-    B_ = d["batch"].cast<int>();
-    cap_ = d["capacity"].cast<int>();
+    a_.L = pd_.get<int>("L");
+    B_ = pd_.get<int>("batch");
+    cap_ = pd_.get<int>("capacity");
     TORCH_CHECK(a_.L > 0 && B_ > 0 && cap_ >= B_, "fragment length, batch and capacity");
-    a_.ds = d["ds"].cast<int>();
-    a_.da = d["da"].cast<int>();
-    a_.dns = d["dns"].cast<int>();
-    const int use_done = d["use_done"].cast<int>();
+    a_.ds = pd_.get<int>("ds");
+    a_.da = pd_.get<int>("da");
+    a_.dns = pd_.get<int>("dns");
+    const int use_done = pd_.get<int>("use_done");
     a_.din = a_.ds + a_.da + a_.dns + use_done;
-    a_.s_all = fptr("s_all", a_.ds == 0);
-    a_.a_all = fptr("a_all", a_.da == 0);
-    a_.ns_all = fptr("ns_all", a_.dns == 0);
-    a_.d_all = fptr("d_all", use_done == 0);
-    a_.prefs_all = fptr("prefs_all");
-    a_.gt_all = fptr("gt_all", true);
+    a_.s_all = pd_.fptr("s_all", a_.ds == 0);
+    a_.a_all = pd_.fptr("a_all", a_.da == 0);
+    a_.ns_all = pd_.fptr("ns_all", a_.dns == 0);
+    a_.d_all = pd_.fptr("d_all", use_done == 0);
+    a_.prefs_all = pd_.fptr("prefs_all");
+    a_.gt_all = pd_.fptr("gt_all", true);
     // reward MLP: flat parameter order W0, b0, W1, b1, ... (the optimizer's flat buffer)
-    py::dict nd = d["net"].cast<py::dict>();
-    auto Ws = nd["W"].cast<std::vector<torch::Tensor>>();
-    auto bs = nd["b"].cast<std::vector<torch::Tensor>>();
-    TORCH_CHECK(!Ws.empty() && Ws.size() <= (size_t)ia::kAirlMaxLayers && Ws.size() == bs.size(), "net: 1..4 layers");
-    ia::AirlNet& n = a_.net;
-    n.n_layers = (int)Ws.size();
-    n.dims[0] = (int)Ws[0].size(1);
-    n.hidden_act = nd["hidden_act"].cast<int>();
-    n.param_off = 0;
-    int o = 0;
-    for (size_t l = 0; l < Ws.size(); ++l) {
-      TORCH_CHECK(Ws[l].is_cuda() && Ws[l].is_contiguous() && Ws[l].scalar_type() == torch::kFloat32, "net weights");
-      TORCH_CHECK(l == 0 || Ws[l].size(1) == Ws[l - 1].size(0), "net: layer widths do not chain");
-      held_.push_back(Ws[l]);
-      held_.push_back(bs[l]);
-      n.dims[l + 1] = (int)Ws[l].size(0);
-      n.W[l] = Ws[l].data_ptr<float>();
-      n.b[l] = bs[l].data_ptr<float>();
-      n.w_off[l] = o;
-      o += (int)Ws[l].numel();
-      n.b_off[l] = o;
-      o += (int)bs[l].numel();
-    }
-    a_.n_params = o;
-    TORCH_CHECK(n.dims[0] == a_.din, "reward-net input width ", n.dims[0], " != gathered width ", a_.din);
-    a_.rmean = fptr("rmean", true);
-    a_.rvar = fptr("rvar", true);
-    if (a_.rmean) {
-      auto c = keep("rcount");
-      TORCH_CHECK(c.scalar_type() == torch::kInt32, "rcount must be int32");
-      a_.rcount = c.data_ptr<int>();
-    }
-    a_.eps = (float)d["eps"].cast<double>();
-    a_.discount = (float)d["discount"].cast<double>();
-    a_.threshold = (float)d["threshold"].cast<double>();
-    a_.noise = (float)d["noise"].cast<double>();
+    a_.net = read_airl_net(pd_, "net", &a_.n_params);
+    TORCH_CHECK(a_.net.dims[0] == a_.din, "reward-net input width ", a_.net.dims[0], " != gathered width ", a_.din);
+    a_.rmean = pd_.fptr("rmean", true);
+    a_.rvar = pd_.fptr("rvar", true);
+    if (a_.rmean) a_.rcount = pd_.iptr("rcount");
+    a_.eps = pd_.getf("eps");
+    a_.discount = pd_.getf("discount");
+    a_.threshold = pd_.getf("threshold");
+    a_.noise = pd_.getf("noise");
     a_.gscale = (float)(1.0 / (double)B_);
     TORCH_CHECK(ia::pref_rm_plan(a_, plan_), "reward net outside the fused kernel's limits (widths <= 64, <= 4 layers, "
                                              "scalar head, <= 128 input columns)");
     // workspaces, sized for `capacity` pairs per minibatch
-    const auto fo = torch::TensorOptions().dtype(torch::kFloat32).device(held_[0].device());
+    const auto fo = torch::TensorOptions().dtype(torch::kFloat32).device(pd_.device());
     const int64_t rows = (int64_t)cap_ * 2 * a_.L;
     const int blocks = ia::pref_rm_blocks(cap_, a_.L);
     ws_.push_back(torch::empty({rows * a_.din}, fo));
@@ -119,19 +69,11 @@ class PrefRmPlan {
     metrics_ = torch::zeros({8}, fo);
     // AdamW (disc.hip) on the optimizer's flat buffers, bias corrections from its device step
     ad_ = ia::DiscAdamArgs{};
-    ad_.n_params = a_.n_params;
-    ad_.params = fptr("params");
-    TORCH_CHECK(held_.back().numel() >= a_.n_params, "flat params smaller than the net");
-    ad_.exp_avg = fptr("exp_avg");
-    ad_.exp_avg_sq = fptr("exp_avg_sq");
-    a_.step = fptr("step");
+    fill_adam(pd_, ad_, a_.n_params, "adam_eps", false);
+    a_.step = pd_.fptr("step");
     ad_.step = a_.step;
-    ad_.lr = (float)d["lr"].cast<double>();
-    ad_.beta1 = (float)d["beta1"].cast<double>();
-    ad_.beta2 = (float)d["beta2"].cast<double>();
-    ad_.eps = (float)d["adam_eps"].cast<double>();
-    ad_.weight_decay = (float)d["weight_decay"].cast<double>();
-    ad_.decoupled = d["decoupled"].cast<bool>() ? 1 : 0;
+    ad_.lr = pd_.getf("lr");
+    ad_.decoupled = pd_.get<bool>("decoupled") ? 1 : 0;
     ad_.grads = grads_.data_ptr<float>();
     ad_.slab = a_.slab;
     ad_.stats_slab = a_.pstats;
@@ -147,9 +89,9 @@ class PrefRmPlan {
   // ([loss, accuracy, ground-truth loss] minibatch means)
   torch::Tensor step(torch::Tensor idx, bool merge) {
     ia::PrefRmArgs a = args(idx, merge);
-    IA_HIP_CHECK_P(ia::pref_rm_gather(a, ia_stream()));
-    IA_HIP_CHECK_P(ia::pref_rm_fwd(a, plan_, 0, ia_stream()));
-    IA_HIP_CHECK_P(ia::pref_rm_bwd(a, plan_, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_gather(a, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_fwd(a, plan_, 0, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_bwd(a, plan_, ia_stream()));
     adam_launch(a, 1, 1);
     return metrics_;
   }
@@ -158,16 +100,16 @@ class PrefRmPlan {
   // gather (+ the column sums -> sums(): all-reduce them before forward(n_total > 0))
   void gather(torch::Tensor idx, bool merge) {
     ia::PrefRmArgs a = args(idx, merge);
-    IA_HIP_CHECK_P(ia::pref_rm_gather(a, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_gather(a, ia_stream()));
   }
   // moments from sums() over n_total rows (0: this rank's rows)
   void forward(torch::Tensor idx, bool merge, int n_total) {
     ia::PrefRmArgs a = args(idx, merge);
-    IA_HIP_CHECK_P(ia::pref_rm_fwd(a, plan_, n_total, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_fwd(a, plan_, n_total, ia_stream()));
   }
   void backward(torch::Tensor idx, bool merge) {
     ia::PrefRmArgs a = args(idx, merge);
-    IA_HIP_CHECK_P(ia::pref_rm_bwd(a, plan_, ia_stream()));
+    IA_HIP_CHECK(ia::pref_rm_bwd(a, plan_, ia_stream()));
     adam_launch(a, 1, 0);
   }
   void apply(torch::Tensor idx) {
@@ -194,12 +136,12 @@ class PrefRmPlan {
       a.cursor = cursor.data_ptr<int>();
       a.idx_stride = P;
       a.merge = merge ? 1 : 0;
-      IA_HIP_CHECK_P(ia::pref_rm_gather(a, ia_stream()));
-      IA_HIP_CHECK_P(ia::pref_rm_fwd(a, plan_, 0, ia_stream()));
-      IA_HIP_CHECK_P(ia::pref_rm_bwd(a, plan_, ia_stream()));
+      IA_HIP_CHECK(ia::pref_rm_gather(a, ia_stream()));
+      IA_HIP_CHECK(ia::pref_rm_fwd(a, plan_, 0, ia_stream()));
+      IA_HIP_CHECK(ia::pref_rm_bwd(a, plan_, ia_stream()));
       adam_launch(a, 1, 1, ep.data_ptr<float>() + (int64_t)mb * 8);
     }
-    IA_HIP_CHECK_P(ia::pref_rm_epoch_end(ep.data_ptr<float>(), all.data_ptr<float>(), n_mb * 8, cursor.data_ptr<int>(),
+    IA_HIP_CHECK(ia::pref_rm_epoch_end(ep.data_ptr<float>(), all.data_ptr<float>(), n_mb * 8, cursor.data_ptr<int>(),
                                          ia_stream()));
   }
 
@@ -216,15 +158,13 @@ class PrefRmPlan {
   }
   void adam_launch(const ia::PrefRmArgs& a, int reduce, int do_adam, float* stats_out = nullptr) {
     ia::DiscAdamArgs d = ad_;
-    d.reduce = reduce;
-    d.adam = do_adam;
     d.nblk = ia::pref_rm_blocks(a.n, a.L);
     d.stats_nblk = a.n;
     d.stats_scale = 1.f / (float)a.n;
-    d.stats_out = reduce ? (stats_out ? stats_out : metrics_.data_ptr<float>()) : nullptr;
-    IA_HIP_CHECK_P(ia::disc_adam(d, ia_stream()));
+    launch_disc_adam(d, reduce, do_adam, reduce ? (stats_out ? stats_out : metrics_.data_ptr<float>()) : nullptr);
   }
-  std::vector<torch::Tensor> held_, ws_;
+  PlanDict pd_;
+  std::vector<torch::Tensor> ws_;
   torch::Tensor sums_, grads_, metrics_;
   ia::PrefRmArgs a_{};
   ia::PrefPlan plan_{};

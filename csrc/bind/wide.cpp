@@ -7,12 +7,6 @@
 
 namespace {
 
-#define IA_HIP_CHECK_W(expr)                                                          \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    TORCH_CHECK(_e == hipSuccess, "HIP error in " #expr ": ", hipGetErrorString(_e)); \
-  } while (0)
-
 // Y = act(X W^T + b)
 torch::Tensor wlin_forward(torch::Tensor X, torch::Tensor W, c10::optional<torch::Tensor> b, int64_t act) {
   IA_CHECK_GPU_F32(X);
@@ -32,7 +26,7 @@ torch::Tensor wlin_forward(torch::Tensor X, torch::Tensor W, c10::optional<torch
   a.act = (int)act;
   auto Y = torch::empty({a.M, a.N}, X.options());
   a.Y = Y.data_ptr<float>();
-  IA_HIP_CHECK_W(ia::wlin_forward(a, ia_stream()));
+  IA_HIP_CHECK(ia::wlin_forward(a, ia_stream()));
   return Y;
 }
 
@@ -61,7 +55,7 @@ torch::Tensor wlin_backward_x(torch::Tensor dZ, torch::Tensor W, c10::optional<t
   }
   auto G = torch::empty({a.M, a.K}, dZ.options());
   a.G = G.data_ptr<float>();
-  IA_HIP_CHECK_W(ia::wlin_backward_x(a, ia_stream()));
+  IA_HIP_CHECK(ia::wlin_backward_x(a, ia_stream()));
   return G;
 }
 
@@ -103,7 +97,7 @@ py::tuple wlin_backward_w(torch::Tensor dZ, torch::Tensor X, bool need_db) {
     a.ws = ws.data_ptr<float>();
     a.cnt = dw_counters(dZ, ia::wlin_dw_tiles(a.N, a.K));
   }
-  IA_HIP_CHECK_W(ia::wlin_backward_w(a, ia_stream()));
+  IA_HIP_CHECK(ia::wlin_backward_w(a, ia_stream()));
   return py::make_tuple(dW, need_db ? py::cast(db) : py::none());
 }
 

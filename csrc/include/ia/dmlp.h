@@ -16,15 +16,32 @@ namespace dmlp {
 constexpr int kRows = 64;  // rows per block (4 waves x 16)
 constexpr int kNW = 4;
 
-__device__ inline void chan_merge(float* rmean, float* rvar, int count, int c, float bmean, float bvar, int n) {
-  // RunningNorm.update_stats (networks.py:94-111), same fp32 operation order
-  const float fc = (float)count, fn = (float)n, tot = (float)(count + n);
-  const float delta = bmean - rmean[c];
-  rmean[c] += delta * fn / tot;
-  float v = rvar[c] * fc;
-  v += bvar * fn;
-  v += delta * delta * fc * fn / tot;
-  rvar[c] = v / tot;
+// ---- LDS plan pieces (host planners and kernels)
+// bf16 weight image of a din -> dout layer: forward [o][i], transposed [i][o]; 16-byte multiples
+__host__ __device__ inline int wf_image_bytes(int din, int dout) { return (pad32(dout) * ld_for_k(din) * 2 + 15) & ~15; }
+__host__ __device__ inline int wt_image_bytes(int din, int dout) { return (pad32(din) * ld_for_k(dout) * 2 + 15) & ~15; }
+// H^T / dZ^T image [feature][row] for nets of width <= dmax; never under the head's [32][row] dZ^T
+__host__ __device__ inline int ht_image_bytes(int dmax, int ld_ht) {
+  const int b = pad32(dmax) * ld_ht * 2;
+  return b < kRows * 32 * 2 ? kRows * 32 * 2 : b;
+}
+// Backward scratch of mlp_backward: HT, dZ x2 (row images), dZT x2, dbs [2][kNW][dmax_pad] + head
+__host__ __device__ inline int bwd_scratch_bytes(int ht_bytes, int rimg_bytes, int dmax_pad) {
+  return 3 * ht_bytes + 2 * rimg_bytes + (2 * kNW * dmax_pad + 16) * 4;
+}
+struct ZImg {  // double-buffered dZ / dZ^T images (address computed per use: see mlp_forward)
+  char* base;
+  int stride;
+  __device__ lbf* operator[](int z) const { return (lbf*)(base + (size_t)z * stride); }
+};
+struct BwdScratch {
+  lbf* HT;
+  ZImg dZ, dZT;
+  lfl* dbs;
+};
+__device__ inline BwdScratch carve_bwd_scratch(char* sc, int ht_bytes, int rimg_bytes) {
+  return BwdScratch{(lbf*)sc, ZImg{sc + ht_bytes, rimg_bytes}, ZImg{sc + ht_bytes + 2 * rimg_bytes, ht_bytes},
+                    (lfl*)(sc + 3 * ht_bytes + 2 * rimg_bytes)};
 }
 
 

@@ -49,6 +49,28 @@ struct DiscLoss {
   float scale;
   float* stats_slab;
 };
+#if defined(__HIPCC__)
+// One row's BCE-with-logits term: dl = dL/dz and the row's six statistics, from the logit h,
+// the label y (1 expert, 0 generator) and the loss scale.
+struct BceRow {
+  float dl;
+  float st[6];
+};
+__device__ __forceinline__ BceRow bce_row(float h, float y, float scale) {
+  const float sg = 1.f / (1.f + expf(-h));
+  const float sp = fmaxf(h, 0.f) + log1pf(expf(-fabsf(h)));  // softplus(z)
+  const bool gen_pred = h < 0.f, gen_true = y == 0.f, correct = gen_pred == gen_true;
+  BceRow b;
+  b.dl = (sg - y) * scale;
+  b.st[0] = sp - h * y;  // BCE-with-logits
+  b.st[1] = correct ? 1.f : 0.f;
+  b.st[2] = gen_pred ? 1.f : 0.f;
+  b.st[3] = (!gen_true && correct) ? 1.f : 0.f;
+  b.st[4] = (gen_true && correct) ? 1.f : 0.f;
+  b.st[5] = sp - h * sg;  // entropy of Bernoulli(sigmoid(z))
+  return b;
+}
+#endif
 
 struct TmlpPlan {
   int rows;       // rows per block = 16 * waves

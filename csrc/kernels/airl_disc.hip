@@ -39,6 +39,8 @@
 
 #include "ia/dmlp.h"
 #include "ia/mfma.h"
+#include "ia/moments.h"
+#include "ia/transition.h"
 #include "launchers.h"
 
 namespace ia {
@@ -46,59 +48,17 @@ namespace {
 
 using namespace dmlp;  // kRows / kNW, staging, MLP forward / backward (ia/dmlp.h)
 constexpr int kGatherRows = 16;  // 8 rows per thread: >= 256 blocks for a 2 x 2048-row batch
-constexpr int kNormPhases = 8;
 // Dynamic LDS the fwd/bwd launch may ask for: a CU's 160 KiB less 8 KiB for the kernel's static
 // arrays (fl, heads, st_w: 6016 bytes).
 constexpr int kAirlLdsLimit = 152 * 1024;
-constexpr int kMomentSums = 4;  // per block and column: S1, S2 under two shifts (airl_gather_kernel)
 
 // ------------------------------------------------------------------ gather
-__device__ __forceinline__ float act_val(const AirlDiscArgs& a, bool expert, int64_t src, int j) {
-  if (a.act_discrete) {
-    const int64_t* acts = expert ? a.e_acts_i : a.g_acts_i;
-    return (int)acts[src] == j ? 1.f : 0.f;
-  }
-  return (expert ? a.e_acts : a.g_acts)[src * a.A + j];
-}
-
-// column c of the base-net input for source row src
-__device__ __forceinline__ float base_col(const AirlDiscArgs& a, bool expert, int64_t src, int c) {
-  const int D = a.D;
-  if (a.use_state) {
-    if (c < D) return (expert ? a.e_obs : a.g_obs)[src * D + c];
-    c -= D;
-  }
-  if (a.use_action) {
-    if (c < a.aw) return act_val(a, expert, src, c);
-    c -= a.aw;
-  }
-  if (a.use_next_state) {
-    if (c < D) return (expert ? a.e_next_obs : a.g_next_obs)[src * D + c];
-    c -= D;
-  }
-  return (expert ? a.e_dones : a.g_dones)[src] ? 1.f : 0.f;
-}
-
-// Shift of the moment sums. The batch variance is formed as S2/n - (S1/n)^2 from fp32 block sums
-// of (v - shift) and (v - shift)^2, which is only accurate when |mean - shift| is not large
-// against the column's spread (a column at 100 +- 1 summed with shift 0 loses three digits of
-// its variance). The running mean is such a shift once it has seen data, but it is 0 on the
-// first update and absent without a normaliser. So, as disc_gather_kernel (disc.hip), every
-// block keeps two pairs of sums: one shifted by the running mean (or 0), one shifted by the
-// minibatch's own first gathered row, which each block re-gathers and airl_norm reads back from
-// row 0 of Xb / S2 / S. airl_norm takes the running-mean pair unless the two variances disagree
-// (see there), so well-centred data gives the bits it always gave.
-// The DP modes all-reduce the sums over ranks and need a shift every rank agrees on: they use
-// the running-mean pair alone. Remaining limitation: there, until the running mean has seen
-// data -- or always, without that normaliser -- an off-centre column's variance keeps that
-// cancellation error.
-//
-// statistics columns: [0, din_b) base input, [din_b, din_b + D) s', [din_b + D, din_b + 2D) s
-// partials[blk] = [S1, S2 (running-mean shift), S1, S2 (row-0 shift)][ncol]
+// statistics columns: [0, din_b) base input, [din_b, din_b + D) s', [din_b + D, din_b + 2D) s;
+// row 0 of the minibatch (the second shift of the moment sums, ia/moments.h) is row 0 of Xb / S2 / S
 __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k) {
   __shared__ float red[2][kMomentSums][128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
-  const int n = 2 * a.mb, D = a.D, nb = a.din_b;
+  const int n = 2 * a.mb, D = a.in.D, nb = a.din_b;
   const int ncol = nb + 2 * D;
   const int r0 = blockIdx.x * kGatherRows;
   const int64_t* e_idx = a.e_idx + (size_t)k * a.mb;
@@ -109,13 +69,13 @@ __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k)
     const int64_t src0 = e_idx[0];  // row 0 of the minibatch is its first expert row
     if (c < nb) {
       shift = a.b_mean ? a.b_mean[c] : 0.f;
-      shift0 = base_col(a, true, src0, c);
+      shift0 = reward_input_col(a.in, a.e, a.g, true, src0, c);
     } else {
       shift = a.p_mean ? a.p_mean[(c - nb) % D] : 0.f;
-      shift0 = c < nb + D ? a.e_next_obs[src0 * D + (c - nb)] : a.e_obs[src0 * D + (c - nb - D)];
+      shift0 = c < nb + D ? a.e.next_obs[src0 * D + (c - nb)] : a.e.obs[src0 * D + (c - nb - D)];
     }
   }
-  float s1 = 0.f, s2 = 0.f, d1 = 0.f, d2 = 0.f;
+  MomentAcc m;
 #pragma unroll
   for (int rr = ph; rr < kGatherRows; rr += 2) {
     const int r = r0 + rr;
@@ -125,42 +85,28 @@ __global__ __launch_bounds__(256) void airl_gather_kernel(AirlDiscArgs a, int k)
     float v = 0.f;
     if (col_ok) {
       if (c < nb) {
-        v = base_col(a, expert, src, c);
+        v = reward_input_col(a.in, a.e, a.g, expert, src, c);
         a.Xb[(size_t)r * nb + c] = v;
       } else if (c < nb + D) {
-        v = (expert ? a.e_next_obs : a.g_next_obs)[src * D + (c - nb)];
+        v = (expert ? a.e.next_obs : a.g.next_obs)[src * D + (c - nb)];
         a.S2[(size_t)r * D + (c - nb)] = v;
       } else {
-        v = (expert ? a.e_obs : a.g_obs)[src * D + (c - nb - D)];
+        v = (expert ? a.e.obs : a.g.obs)[src * D + (c - nb - D)];
         a.S[(size_t)r * D + (c - nb - D)] = v;
       }
-      const float dv = v - shift;
-      s1 += dv;
-      s2 += dv * dv;
-      const float dv0 = v - shift0;
-      d1 += dv0;
-      d2 += dv0 * dv0;
+      m.add(v, shift, shift0);
     }
     // raw actions for log pi (Gaussian values / categorical index) and dones (each row is
     // handled by one phase)
     if (c < a.aw_pi) {
       float av;
-      if (a.act_discrete) av = (float)(expert ? a.e_acts_i : a.g_acts_i)[src];
-      else av = (expert ? a.e_acts : a.g_acts)[src * a.A + c];
+      if (a.in.act_discrete) av = (float)(expert ? a.e.acts_i : a.g.acts_i)[src];
+      else av = (expert ? a.e.acts : a.g.acts)[src * a.A + c];
       a.Act[(size_t)r * a.aw_pi + c] = av;
     }
-    if (c == 127) a.Done[r] = (expert ? a.e_dones : a.g_dones)[src] ? 1.f : 0.f;
+    if (c == 127) a.Done[r] = (expert ? a.e.dones : a.g.dones)[src] ? 1.f : 0.f;
   }
-  red[ph][0][c] = s1;
-  red[ph][1][c] = s2;
-  red[ph][2][c] = d1;
-  red[ph][3][c] = d2;
-  __syncthreads();
-  if (ph == 0 && col_ok) {
-    float* out = a.partials + (size_t)blockIdx.x * kMomentSums * ncol;
-#pragma unroll
-    for (int q = 0; q < kMomentSums; ++q) out[q * ncol + c] = red[0][q][c] + red[1][q][c];
-  }
+  store_block_moments(red, m, ph, c, col_ok, a.partials, ncol);
 }
 
 // ------------------------------------------------------------------ norms
@@ -169,64 +115,21 @@ __device__ __forceinline__ void put_nrm(float* nrm, int slot, int c, const float
   nrm[slot * 256 + 128 + c] = mean ? rsqrtf(var[c] + eps) : 1.f;
 }
 
-// Phase ph's sums of the first NS partial rows of blocks ph, ph + 8, ... for one column, added
-// in block order; the loads of four blocks are issued together (the loop is latency-bound).
-template <int NS>
-__device__ __forceinline__ void sum_partials(const float* __restrict__ p, int ph, int nblk, int ncol,
-                                             double (&s)[kMomentSums]) {
-  constexpr int U = 4;
-  const size_t step = (size_t)kNormPhases * kMomentSums * ncol;
-  int b = ph;
-  for (; b + (U - 1) * kNormPhases < nblk; b += U * kNormPhases, p += U * step) {
-    float v[U][NS];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int q = 0; q < NS; ++q) v[u][q] = p[u * step + (size_t)q * ncol];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int q = 0; q < NS; ++q) s[q] += (double)v[u][q];
-  }
-  for (; b < nblk; b += kNormPhases, p += step)
-#pragma unroll
-    for (int q = 0; q < NS; ++q) s[q] += (double)p[(size_t)q * ncol];
-}
-
-// The two variances of a column (see airl_gather_kernel) agree to rounding when the running
-// mean is a fair centre of the batch; then the running-mean pair is used, as it always was.
-// Where they differ by more than kMomentRtol of the row-0 variance, the running-mean pair has
-// lost that much to cancellation and the row-0 pair, whose error stays near fp32 rounding
-// whatever the column's offset, is used instead (the threshold of disc_norm_kernel).
-constexpr double kMomentRtol = 1e-5;
-
-// 1024 threads = 8 block-phases x 128 columns (fixed-order reduction, as disc_norm_kernel)
+// 1024 threads = 8 block-phases x 128 columns (fixed-order reduction, ia/moments.h)
 __global__ __launch_bounds__(128 * kNormPhases) void airl_norm_kernel(AirlDiscArgs a, int mode, int n_total) {
   __shared__ double red[kNormPhases][kMomentSums][128];
   __shared__ float bm[128], bv[128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
-  const int D = a.D, nb = a.din_b, ncol = nb + 2 * D;
+  const int D = a.in.D, nb = a.din_b, ncol = nb + 2 * D;
   const int n = mode == 2 ? n_total : 2 * a.mb;
-  if (mode != 2) {
-    double s[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
-    if (c < ncol) {
-      const float* p = a.partials + (size_t)ph * kMomentSums * ncol + c;
-      if (mode == 0) sum_partials<kMomentSums>(p, ph, a.gather_blocks, ncol, s);
-      else sum_partials<2>(p, ph, a.gather_blocks, ncol, s);  // the DP sums carry the shared shift only
-    }
-#pragma unroll
-    for (int q = 0; q < kMomentSums; ++q) red[ph][q][c] = s[q];
-    __syncthreads();
-  }
+  if (mode != 2) phase_sums(red, a.partials, a.gather_blocks, ncol, c, ph, mode == 0);
   if (ph == 0 && c < ncol) {
     double S[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
     if (mode == 2) {
       S[0] = a.sums[c];
       S[1] = a.sums[ncol + c];
     } else {
-      for (int q = 0; q < kNormPhases; ++q)
-#pragma unroll
-        for (int j = 0; j < kMomentSums; ++j) S[j] += red[q][j][c];
+      column_sums(red, c, S);
     }
     if (mode == 1) {
       a.sums[c] = S[0];
@@ -235,21 +138,10 @@ __global__ __launch_bounds__(128 * kNormPhases) void airl_norm_kernel(AirlDiscAr
       float shift = 0.f;
       if (c < nb) shift = a.b_mean ? a.b_mean[c] : 0.f;
       else shift = a.p_mean ? a.p_mean[(c - nb) % D] : 0.f;
-      const double m = S[0] / n;
-      double var = S[1] / n - m * m;
-      if (var < 0.0) var = 0.0;
-      bm[c] = (float)((double)shift + m);
-      bv[c] = (float)var;
-      if (mode == 0) {
-        const double m0 = S[2] / n;
-        double var0 = S[3] / n - m0 * m0;
-        if (var0 < 0.0) var0 = 0.0;
-        if (fabs(var - var0) > kMomentRtol * var0) {
-          const float row0 = c < nb ? a.Xb[c] : c < nb + D ? a.S2[c - nb] : a.S[c - nb - D];
-          bm[c] = (float)((double)row0 + m0);
-          bv[c] = (float)var0;
-        }
-      }
+      const float* row0 = c < nb ? a.Xb + c : c < nb + D ? a.S2 + (c - nb) : a.S + (c - nb - D);
+      const BatchMoments b = batch_moments(S, n, shift, row0, mode == 0);
+      bm[c] = b.mean;
+      bv[c] = b.var;
     }
   }
   if (mode == 1) return;
@@ -295,7 +187,7 @@ __global__ __launch_bounds__(128) void airl_q_merge_kernel(AirlDiscArgs a, int c
   const int c = threadIdx.x;
   const int qc = *a.q_count;
   __syncthreads();
-  if (c < a.D) {
+  if (c < a.in.D) {
     for (int j = 0; j < count; ++j) {
       float* nrm = a.nrm + (size_t)j * stride;
       const float* dq = a.q_defer + (size_t)j * stride;
@@ -331,11 +223,11 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
     }
   }
   // backward scratch aliases the policy images (the policy pass is over by then)
-  char* sc = smem + p.scratch_off;
-  lbf* HT = (lbf*)(sc);
-  lbf* dZ[2] = {(lbf*)(sc + p.ht_bytes), (lbf*)(sc + p.ht_bytes + p.rimg_bytes)};
-  lbf* dZT[2] = {(lbf*)(sc + p.ht_bytes + 2 * p.rimg_bytes), (lbf*)(sc + p.ht_bytes + 2 * p.rimg_bytes + p.ht_bytes)};
-  lfl* dbs = (lfl*)(sc + 3 * p.ht_bytes + 2 * p.rimg_bytes);
+  const BwdScratch bs = carve_bwd_scratch(smem + p.scratch_off, p.ht_bytes, p.rimg_bytes);
+  lbf* HT = bs.HT;
+  lbf* dZ[2] = {bs.dZ[0], bs.dZ[1]};
+  lbf* dZT[2] = {bs.dZT[0], bs.dZT[1]};
+  lfl* dbs = bs.dbs;
 
   const int n = 2 * a.mb;
   const int row0 = blockIdx.x * kRows;
@@ -367,10 +259,10 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
       if (q > 0) stage_net(q, true);
     }
   }
-  stage_rows(Pimg[0], p.ldp, a.S, a.D, n, row0, a.nrm + 0 * 256);
+  stage_rows(Pimg[0], p.ldp, a.S, a.in.D, n, row0, a.nrm + 0 * 256);
   stage_rows(Bh[0], ld_for_k(a.din_b), a.Xb, a.din_b, n, row0, a.nrm + 1 * 256);
-  stage_rows(Qh[0], ld_for_k(a.D), a.S2, a.D, n, row0, a.nrm + 2 * 256);
-  stage_rows(Rh[0], ld_for_k(a.D), a.S, a.D, n, row0, a.nrm + 3 * 256);
+  stage_rows(Qh[0], ld_for_k(a.in.D), a.S2, a.in.D, n, row0, a.nrm + 2 * 256);
+  stage_rows(Rh[0], ld_for_k(a.in.D), a.S, a.in.D, n, row0, a.nrm + 3 * 256);
   __syncthreads();
 
   unsigned long long t_1 = stamp ? clock64() : 0;
@@ -404,7 +296,7 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
       float lp = 0.f;
       if (gr < n) {
         const int A = a.A;
-        if (a.act_discrete) {
+        if (a.in.act_discrete) {
           float mx = -INFINITY;
           for (int j = 0; j < A; ++j) mx = fmaxf(mx, heads[r][j]);
           float zs = 0.f;
@@ -441,20 +333,12 @@ __global__ __launch_bounds__(64 * kNW) void airl_fwd_bwd_kernel(AirlDiscArgs a, 
     if (gr < n) {
       const float d = a.Done[gr];
       const float h = fl[1][r] + a.gamma * (1.f - d) * fl[2][r] - fl[3][r] - fl[0][r];
-      const float y = gr < a.mb ? 1.f : 0.f;
-      const float sg = 1.f / (1.f + expf(-h));
-      const float sp = fmaxf(h, 0.f) + log1pf(expf(-fabsf(h)));  // softplus(z)
-      const float dl = (sg - y) * a.scale;
-      g_b = dl;
-      g_p1 = a.gamma * (1.f - d) * dl;
-      g_p2 = -dl;
-      const bool gen_pred = h < 0.f, gen_true = y == 0.f, correct = gen_pred == gen_true;
-      st[0] = sp - h * y;
-      st[1] = correct ? 1.f : 0.f;
-      st[2] = gen_pred ? 1.f : 0.f;
-      st[3] = (!gen_true && correct) ? 1.f : 0.f;
-      st[4] = (gen_true && correct) ? 1.f : 0.f;
-      st[5] = sp - h * sg;
+      const BceRow b = bce_row(h, gr < a.mb ? 1.f : 0.f, a.scale);
+      g_b = b.dl;
+      g_p1 = a.gamma * (1.f - d) * b.dl;
+      g_p2 = -b.dl;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) st[q] = b.st[q];
     }
     fl[4][r] = g_b;
     fl[5][r] = g_p1;
@@ -514,25 +398,22 @@ bool airl_plan(const AirlDiscArgs& a, AirlPlan& p) {
   }
   if (a.base.dims[a.base.n_layers] != 1 || a.pot.dims[a.pot.n_layers] != 1) return false;
   if (a.pol.dims[a.pol.n_layers] != a.A || a.A > 16) return false;
-  if (a.din_b + 2 * a.D > 128) return false;
+  if (a.din_b + 2 * a.in.D > 128) return false;
   p.ldp = ld_for_k(pmax);
   p.ldr = ld_for_k(rmax);
   p.ld_ht = ld_for_k(kRows);
   p.dmax_pad = pad32(rmax);
-  const int wmax = pmax > rmax ? pmax : rmax;
   p.pimg_bytes = kRows * p.ldp * 2;
   p.rimg_bytes = kRows * p.ldr * 2;
-  p.ht_bytes = pad32(rmax) * p.ld_ht * 2;
-  if (p.ht_bytes < kRows * 32 * 2) p.ht_bytes = kRows * 32 * 2;
-  (void)wmax;
-  auto wf_bytes = [&](int q, int l) { return (pad32(nets[q]->dims[l + 1]) * ld_for_k(nets[q]->dims[l]) * 2 + 15) & ~15; };
-  auto wt_bytes = [&](int q, int l) { return (pad32(nets[q]->dims[l]) * ld_for_k(nets[q]->dims[l + 1]) * 2 + 15) & ~15; };
+  p.ht_bytes = ht_image_bytes(rmax, p.ld_ht);
+  auto wf_bytes = [&](int q, int l) { return wf_image_bytes(nets[q]->dims[l], nets[q]->dims[l + 1]); };
+  auto wt_bytes = [&](int q, int l) { return wt_image_bytes(nets[q]->dims[l], nets[q]->dims[l + 1]); };
   // row images, packed by width: the inputs of every layer of the base and of both potential passes
   int img_bytes = 0;
   for (int l = 0; l < a.base.n_layers; ++l) img_bytes += kRows * ld_for_k(a.base.dims[l]) * 2;
   for (int l = 0; l < a.pot.n_layers; ++l) img_bytes += 2 * kRows * ld_for_k(a.pot.dims[l]) * 2;
   const int pol_scratch = 2 * p.pimg_bytes;
-  const int bwd_scratch = 3 * p.ht_bytes + 2 * p.rimg_bytes + (2 * kNW * p.dmax_pad + 16) * 4;
+  const int bwd_scratch = bwd_scratch_bytes(p.ht_bytes, p.rimg_bytes, p.dmax_pad);
   // dZT images are [k][row] with k < 32 here (pad32(dout) of the backward operand <= pad32(rmax))
   const int scratch_bytes = ((pol_scratch > bwd_scratch ? pol_scratch : bwd_scratch) + 15) & ~15;
   // weight images: all resident where that fits, else one pass's images at a time in one region

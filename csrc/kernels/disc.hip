@@ -21,139 +21,39 @@
 // Every reduction is in a fixed order: replicas are bitwise reproducible.
 #include <hip/hip_runtime.h>
 
+#include "ia/moments.h"
+#include "ia/transition.h"
 #include "launchers.h"
 
 namespace ia {
 namespace {
 
 constexpr int kGatherRows = 64;  // rows per gather block (>= 256 blocks for a 16k batch)
-constexpr int kMomentSums = 4;   // per block and column: S1, S2 under two shifts (disc_gather_kernel)
 
-__device__ __forceinline__ float load_act(const DiscGatherArgs& a, bool expert, int64_t src, int j, int aw) {
-  if (a.act_discrete) {
-    const int64_t* acts = expert ? a.e_acts_i : a.g_acts_i;
-    return (int)acts[src] == j ? 1.f : 0.f;
-  }
-  const float* acts = expert ? a.e_acts : a.g_acts;
-  return acts[src * aw + j];
-}
-
-// Value of column c of the reward-net input for source row src of the expert/gen set.
-__device__ __forceinline__ float gather_col(const DiscGatherArgs& a, bool expert, int64_t src, int c) {
-  const int D = a.obs_dim, aw = a.act_width;
-  if (a.use_state) {
-    if (c < D) return (expert ? a.e_obs : a.g_obs)[src * D + c];
-    c -= D;
-  }
-  if (a.use_action) {
-    if (c < aw) return load_act(a, expert, src, c, aw);
-    c -= aw;
-  }
-  if (a.use_next_state) {
-    if (c < D) return (expert ? a.e_next_obs : a.g_next_obs)[src * D + c];
-    c -= D;
-  }
-  return (expert ? a.e_dones : a.g_dones)[src] ? 1.f : 0.f;
-}
-
-// Shift of the moment sums. The batch variance is formed as S2/n - (S1/n)^2 from fp32 block
-// sums of (v - shift) and (v - shift)^2, which is only accurate when |mean - shift| is not
-// large against the column's spread (a column at 100 +- 1 summed with shift 0 loses three
-// digits of its variance). The running mean is such a shift once it has seen data, but it is
-// 0 on the first update and absent when the reward net has no input normaliser. So every
-// block keeps two pairs of sums: one shifted by the running mean (or 0), one shifted by the
-// minibatch's own first gathered row, which each block re-gathers and disc_norm reads back
-// from X row 0. disc_norm takes the running-mean pair unless the two variances disagree (see
-// there), so well-centred data gives the bits it always gave.
-// The DP modes all-reduce the sums over ranks and need a shift every rank agrees on: they
-// use the running-mean pair alone. Remaining limitation: there, until the running mean has
-// seen data -- or always, without a reward normaliser -- an off-centre column's variance keeps
-// that cancellation error.
-//
-// Block: 256 threads = 2 row phases x 128 columns; rows [blk*64, blk*64+64).
-// partials[blk] = [S1, S2 (running-mean shift), S1, S2 (row-0 shift)][din]
+// Block: 256 threads = 2 row phases x 128 columns; rows [blk*64, blk*64+64). The two pairs of
+// moment sums and their shifts: ia/moments.h.
 __global__ __launch_bounds__(256) void disc_gather_kernel(DiscGatherArgs a) {
-  __shared__ float red[2][4][128];
+  __shared__ float red[2][kMomentSums][128];
   const int c = threadIdx.x & 127, ph = threadIdx.x >> 7;
   const int n = 2 * a.mb;
   const int r0 = blockIdx.x * kGatherRows;
   const bool col_ok = c < a.din;
   const float shift = col_ok && a.shift ? a.shift[c] : 0.f;
-  const float shift0 = col_ok ? gather_col(a, true, a.e_idx[0], c) : 0.f;
-  float s1 = 0.f, s2 = 0.f, d1 = 0.f, d2 = 0.f;
+  const float shift0 = col_ok ? reward_input_col(a.in, a.e, a.g, true, a.e_idx[0], c) : 0.f;
+  MomentAcc m;
   if (col_ok) {
     for (int rr = ph; rr < kGatherRows; rr += 2) {
       const int r = r0 + rr;
       if (r >= n) break;
       const bool expert = r < a.mb;
       const int64_t src = expert ? a.e_idx[r] : a.g_idx[r - a.mb];
-      const float v = gather_col(a, expert, src, c);
+      const float v = reward_input_col(a.in, a.e, a.g, expert, src, c);
       a.X[(size_t)r * a.din + c] = v;
-      const float dv = v - shift;
-      s1 += dv;
-      s2 += dv * dv;
-      const float dv0 = v - shift0;
-      d1 += dv0;
-      d2 += dv0 * dv0;
+      m.add(v, shift, shift0);
     }
   }
-  red[ph][0][c] = s1;
-  red[ph][1][c] = s2;
-  red[ph][2][c] = d1;
-  red[ph][3][c] = d2;
-  __syncthreads();
-  if (ph == 0 && col_ok) {
-    float* out = a.partials + (size_t)blockIdx.x * kMomentSums * a.din;
-#pragma unroll
-    for (int k = 0; k < kMomentSums; ++k) out[k * a.din + c] = red[0][k][c] + red[1][k][c];
-  }
+  store_block_moments(red, m, ph, c, col_ok, a.partials, a.din);
 }
-
-__device__ __forceinline__ void chan_merge(float* rmean, float* rvar, int count, int c, float bmean, float bvar, int n) {
-  // RunningNorm.update_stats (networks.py:94-111) in the same operation order (fp32)
-  const float fc = (float)count, fn = (float)n, tot = (float)(count + n);
-  const float delta = bmean - rmean[c];
-  rmean[c] += delta * fn / tot;
-  float v = rvar[c] * fc;
-  v += bvar * fn;
-  v += delta * delta * fc * fn / tot;
-  rvar[c] = v / tot;
-}
-
-// 1024 threads = 8 block-phases x 128 columns: phase p sums partial blocks p, p+8, ... in
-// order, then the 8 phase sums are added in phase order (fixed order: deterministic).
-constexpr int kNormPhases = 8;
-
-// Phase ph's sums of the first NS partial rows of blocks ph, ph + 8, ... for one column, added
-// in block order; the loads of four blocks are issued together (the loop is latency-bound).
-template <int NS>
-__device__ __forceinline__ void sum_partials(const float* __restrict__ p, int ph, int nblk, int din,
-                                             double (&s)[kMomentSums]) {
-  constexpr int U = 4;
-  const size_t step = (size_t)kNormPhases * kMomentSums * din;
-  int b = ph;
-  for (; b + (U - 1) * kNormPhases < nblk; b += U * kNormPhases, p += U * step) {
-    float v[U][NS];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int k = 0; k < NS; ++k) v[u][k] = p[u * step + (size_t)k * din];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int k = 0; k < NS; ++k) s[k] += (double)v[u][k];
-  }
-  for (; b < nblk; b += kNormPhases, p += step)
-#pragma unroll
-    for (int k = 0; k < NS; ++k) s[k] += (double)p[(size_t)k * din];
-}
-
-// The two variances of a column (see disc_gather_kernel) agree to rounding when the running
-// mean is a fair centre of the batch; then the running-mean pair is used, as it always was.
-// Where they differ by more than kMomentRtol of the row-0 variance, the running-mean pair
-// has lost that much to cancellation and the row-0 pair, whose error stays near fp32
-// rounding whatever the column's offset, is used instead.
-constexpr double kMomentRtol = 1e-5;
 
 __global__ __launch_bounds__(128 * kNormPhases) void disc_norm_kernel(DiscNormArgs a) {
   __shared__ double red[kNormPhases][kMomentSums][128];
@@ -161,52 +61,27 @@ __global__ __launch_bounds__(128 * kNormPhases) void disc_norm_kernel(DiscNormAr
   const int n = a.mode == 2 ? a.n_total : 2 * a.mb;
   const int rc = a.rew_count ? *a.rew_count : 0;
   const int pc = a.pol_count ? *a.pol_count : 0;
-  if (a.mode != 2) {
-    double s[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
-    if (c < a.din) {
-      const float* p = a.partials + (size_t)ph * kMomentSums * a.din + c;
-      if (a.mode == 0) sum_partials<kMomentSums>(p, ph, a.nblk, a.din, s);
-      else sum_partials<2>(p, ph, a.nblk, a.din, s);  // the DP sums carry the shared shift only
-    }
-#pragma unroll
-    for (int k = 0; k < kMomentSums; ++k) red[ph][k][c] = s[k];
-    __syncthreads();
-  }
+  if (a.mode != 2) phase_sums(red, a.partials, a.nblk, a.din, c, ph, a.mode == 0);
   if (ph == 0 && c < a.din) {
     double S[kMomentSums] = {0.0, 0.0, 0.0, 0.0};
     if (a.mode == 2) {
       S[0] = a.sums[c];
       S[1] = a.sums[a.din + c];
     } else {
-      for (int q = 0; q < kNormPhases; ++q)
-#pragma unroll
-        for (int k = 0; k < kMomentSums; ++k) S[k] += red[q][k][c];
+      column_sums(red, c, S);
     }
     if (a.mode == 1) {
       a.sums[c] = S[0];
       a.sums[a.din + c] = S[1];
     } else {
-      const double shift = a.shift ? (double)a.shift[c] : 0.0;
-      const double m = S[0] / n;
-      double var = S[1] / n - m * m;
-      if (var < 0.0) var = 0.0;
-      float bmean = (float)(shift + m), bvar = (float)var;
-      if (a.mode == 0) {
-        const double m0 = S[2] / n;
-        double var0 = S[3] / n - m0 * m0;
-        if (var0 < 0.0) var0 = 0.0;
-        if (fabs(var - var0) > kMomentRtol * var0) {
-          bmean = (float)((double)a.X[c] + m0);
-          bvar = (float)var0;
-        }
-      }
-      if (a.rew_mean) chan_merge(a.rew_mean, a.rew_var, rc, c, bmean, bvar, n);
+      const BatchMoments b = batch_moments(S, n, a.shift ? a.shift[c] : 0.f, a.X + c, a.mode == 0);
+      if (a.rew_mean) chan_merge(a.rew_mean, a.rew_var, rc, c, b.mean, b.var, n);
       if (a.pol_defer && c < a.pol_cols) {
-        a.pol_defer[c] = bmean;
-        a.pol_defer[a.pol_cols + c] = bvar;
+        a.pol_defer[c] = b.mean;
+        a.pol_defer[a.pol_cols + c] = b.var;
         if (c == 0) a.pol_defer[2 * a.pol_cols] = (float)n;
       } else if (a.pol_mean && c < a.pol_cols) {
-        chan_merge(a.pol_mean, a.pol_var, pc, c, bmean, bvar, n);
+        chan_merge(a.pol_mean, a.pol_var, pc, c, b.mean, b.var, n);
       }
     }
   }

@@ -27,19 +27,25 @@ int tmlp_disc_blocks(const MLPDesc& d, int B);
 hipError_t tmlp_disc_fwd_bwd(const MLPDesc& d, const float* X, int B, const DiscLoss& dl, float* slab, hipStream_t s);
 
 // ---- disc.hip: fused discriminator update
-struct DiscGatherArgs {
-  int mb;  // rows per side: X holds 2*mb rows, expert first
-  int din, obs_dim, act_width;
+// One side (expert set / generator replay ring) of the transitions a reward net is trained on.
+struct TransitionSrc {
+  const float *obs, *next_obs, *acts;  // acts: Box actions [rows][aw] (null for Discrete)
+  const int64_t* acts_i;               // Discrete action ids [rows] (null for Box)
+  const bool* dones;
+};
+// Column layout of a reward-net input row: [obs | act or one-hot | next_obs | done], each part optional.
+struct RewardInputLayout {
+  int D, aw;  // obs dim, action width (Box dim or n_actions)
   int use_state, use_action, use_next_state, use_done;
   int act_discrete;
+};
+struct DiscGatherArgs {
+  int mb;  // rows per side: X holds 2*mb rows, expert first
+  int din;
+  RewardInputLayout in;
   const int64_t* e_idx;
   const int64_t* g_idx;
-  const float *e_obs, *e_next_obs, *e_acts;
-  const int64_t* e_acts_i;
-  const bool* e_dones;
-  const float *g_obs, *g_next_obs, *g_acts;
-  const int64_t* g_acts_i;
-  const bool* g_dones;
+  TransitionSrc e, g;  // expert, generator
   const float* shift;  // per-column shift for the moment sums (running mean) or null
   float* X;            // [2*mb][din]
   float* partials;     // [nblk][4][din]: S1, S2 shifted by `shift`, S1, S2 shifted by X row 0
@@ -100,22 +106,16 @@ struct AirlNet {
 };
 struct AirlDiscArgs {
   int mb;         // rows per side (2 * mb per minibatch, expert first)
-  int D, A;       // obs dim, action dim (Box) / n_actions (Discrete)
-  int aw;         // action width in the base input (A, or n_actions one-hot)
+  int A;          // action dim (Box) / n_actions (Discrete)
   int aw_pi;      // stored action width for log pi (A, or 1: the index)
-  int act_discrete;
-  int use_state, use_action, use_next_state, use_done, din_b;
+  RewardInputLayout in;  // base-net input (in.aw = A: Box width, or n_actions one-hot)
+  int din_b;             // its width
   const int64_t* e_idx;  // [B] (minibatch k uses [k * mb, (k + 1) * mb))
   const int64_t* g_idx;
-  const float *e_obs, *e_next_obs, *e_acts;
-  const int64_t* e_acts_i;
-  const bool* e_dones;
-  const float *g_obs, *g_next_obs, *g_acts;
-  const int64_t* g_acts_i;
-  const bool* g_dones;
+  TransitionSrc e, g;  // expert, generator
   // gathered minibatch
   float *Xb, *S, *S2, *Act, *Done;
-  float* partials;  // [gather blocks][2][din_b + 2 D]
+  float* partials;  // [gather blocks][4][din_b + 2 D] (kMomentSums sums per column, ia/moments.h)
   int gather_blocks;
   double* sums;     // [2][din_b + 2 D] (DP modes)
   // RunningNorms: b base input, p potential, q policy features (null = none)

@@ -31,6 +31,7 @@
 
 #include "ia/dmlp.h"
 #include "ia/mfma.h"
+#include "ia/moments.h"
 #include "launchers.h"
 
 namespace ia {
@@ -180,30 +181,15 @@ struct HImg {  // row image of layer l's input (the output layer reuses the last
   int bytes, last;
   __device__ lbf* operator[](int l) const { return (lbf*)(base + (size_t)min(l, last) * bytes); }
 };
-struct ZImg {  // double-buffered dZ / dZ^T images
-  char* base;
-  int stride;
-  __device__ lbf* operator[](int z) const { return (lbf*)(base + (size_t)z * stride); }
-};
 struct Imgs {
   WImg Wf, Wt;
   HImg H;
-  lbf* HT;
-  ZImg dZ, dZT;
-  lfl* dbs;
+  BwdScratch s;  // HT, dZ, dZT, dbs (ia/dmlp.h)
 };
 
 __device__ __forceinline__ Imgs carve(char* smem, const PrefPlan& p, int n_layers) {
-  Imgs m;
-  m.Wf = WImg{smem, p.wf_off};
-  m.Wt = WImg{smem, p.wt_off};
-  m.H = HImg{smem + p.rimg_off, p.rimg_bytes, n_layers - 1};
-  char* sc = smem + p.scratch_off;
-  m.HT = (lbf*)(sc);
-  m.dZ = ZImg{sc + p.ht_bytes, p.rimg_bytes};
-  m.dZT = ZImg{sc + p.ht_bytes + 2 * p.rimg_bytes, p.ht_bytes};
-  m.dbs = (lfl*)(sc + 3 * p.ht_bytes + 2 * p.rimg_bytes);
-  return m;
+  return Imgs{WImg{smem, p.wf_off}, WImg{smem, p.wt_off}, HImg{smem + p.rimg_off, p.rimg_bytes, n_layers - 1},
+              carve_bwd_scratch(smem + p.scratch_off, p.ht_bytes, p.rimg_bytes)};
 }
 
 // moments from sums (the gather's; under data parallelism all-reduced over n_total rows)
@@ -221,14 +207,12 @@ __global__ __launch_bounds__(64 * kNW) void pref_fwd_kernel(PrefRmArgs a, PrefPl
     if (threadIdx.x < 128) {
       float mean = 0.f, rstd = 1.f;
       if (c < a.din) {
-        const double S1 = a.sums[c], S2 = a.sums[a.din + c];
+        const double S[kMomentSums] = {a.sums[c], a.sums[a.din + c], 0.0, 0.0};  // the running-mean pair alone
         const int n = n_total > 0 ? n_total : rows;
         float rm = a.old_mv[c], rv = a.old_mv[128 + c];
         if (a.merge) {
-          const double bm = S1 / n;
-          double bv = S2 / n - bm * bm;
-          if (bv < 0.0) bv = 0.0;
-          chan_merge(&rm, &rv, a.old_cnt[0], 0, (float)((double)a.old_mv[c] + bm), (float)bv, n);
+          const BatchMoments b = batch_moments(S, n, a.old_mv[c], nullptr, false);
+          chan_merge(&rm, &rv, a.old_cnt[0], 0, b.mean, b.var, n);
         }
         mean = rm;
         rstd = rsqrtf(rv + a.eps);
@@ -344,7 +328,7 @@ __global__ __launch_bounds__(64 * kNW) void pref_bwd_kernel(PrefRmArgs a, PrefPl
   __syncthreads();
   mlp_forward(net, m.H, p.ldr, m.Wf, (lfl*)out, 1);  // hidden images for the backward
   float* slab_row = a.slab + (size_t)blockIdx.x * a.n_params;
-  mlp_backward(net, m.H, p.ldr, m.Wt, (const lfl*)dy, m.HT, p.ld_ht, m.dZ, m.dZT, m.dbs, p.dmax_pad, slab_row, false);
+  mlp_backward(net, m.H, p.ldr, m.Wt, (const lfl*)dy, m.s.HT, p.ld_ht, m.s.dZ, m.s.dZT, m.s.dbs, p.dmax_pad, slab_row, false);
 }
 
 __global__ void pref_epoch_end_kernel(const float* __restrict__ metrics, float* __restrict__ all, int n, int* cursor) {
@@ -368,33 +352,33 @@ bool pref_rm_plan(const PrefRmArgs& a, PrefPlan& p) {
   const AirlNet& n = a.net;
   if (n.n_layers < 1 || n.n_layers > kAirlMaxLayers) return false;
   int rmax = 0;
+  // layer widths <= 64; the input <= 128 columns (the gather's tile and the nrm / old_mv slots).
+  // Every image below is sized from rmax, the input included, and the LDS bound decides.
   for (int l = 0; l <= n.n_layers; ++l) {
-    if (n.dims[l] <= 0 || n.dims[l] > 64) return false;
+    if (n.dims[l] <= 0 || n.dims[l] > (l == 0 ? 128 : 64)) return false;
     rmax = rmax > n.dims[l] ? rmax : n.dims[l];
   }
-  if (n.dims[n.n_layers] != 1 || n.dims[0] != a.din || a.din > 128 || a.L < 1) return false;
+  if (n.dims[n.n_layers] != 1 || n.dims[0] != a.din || a.L < 1) return false;
   p.ldr = ld_for_k(rmax);
   p.ld_ht = ld_for_k(kRows);
   p.dmax_pad = pad32(rmax);
   p.rimg_bytes = kRows * p.ldr * 2;
-  p.ht_bytes = pad32(rmax) * p.ld_ht * 2;
-  if (p.ht_bytes < kRows * 32 * 2) p.ht_bytes = kRows * 32 * 2;
+  p.ht_bytes = ht_image_bytes(rmax, p.ld_ht);
   int off = 0;
   for (int l = 0; l < kAirlMaxLayers; ++l) {
     p.wf_off[l] = p.wt_off[l] = 0;
     if (l >= n.n_layers) continue;
-    const int din = n.dims[l], dout = n.dims[l + 1];
     p.wf_off[l] = off;
-    off += (pad32(dout) * ld_for_k(din) * 2 + 15) & ~15;
+    off += wf_image_bytes(n.dims[l], n.dims[l + 1]);
     if (l > 0) {
       p.wt_off[l] = off;
-      off += (pad32(din) * ld_for_k(dout) * 2 + 15) & ~15;
+      off += wt_image_bytes(n.dims[l], n.dims[l + 1]);
     }
   }
   p.rimg_off = off;
   off += n.n_layers * p.rimg_bytes;
   p.scratch_off = off;
-  off += (3 * p.ht_bytes + 2 * p.rimg_bytes + (2 * kNW * p.dmax_pad + 16) * 4 + 15) & ~15;
+  off += (bwd_scratch_bytes(p.ht_bytes, p.rimg_bytes, p.dmax_pad) + 15) & ~15;
   p.lds_bytes = off;
   return p.lds_bytes <= 128 * 1024;
 }

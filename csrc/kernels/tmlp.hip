@@ -194,17 +194,10 @@ __global__ __launch_bounds__(64 * NW) void tmlp_bwd_kernel(MLPDesc d, TmlpPlan p
           if constexpr (kDisc) {
             dy = 0.f;
             if (gr < B && col == 0) {
-              const float y = gr < dl.n_expert ? 1.f : 0.f;
-              const float sg = 1.f / (1.f + expf(-h));
-              const float sp = fmaxf(h, 0.f) + log1pf(expf(-fabsf(h)));  // softplus(z)
-              dy = (sg - y) * dl.scale;
-              const bool gen_pred = h < 0.f, gen_true = y == 0.f, correct = gen_pred == gen_true;
-              st[0] += sp - h * y;  // BCE-with-logits
-              st[1] += correct ? 1.f : 0.f;
-              st[2] += gen_pred ? 1.f : 0.f;
-              st[3] += (!gen_true && correct) ? 1.f : 0.f;
-              st[4] += (gen_true && correct) ? 1.f : 0.f;
-              st[5] += sp - h * sg;  // entropy of Bernoulli(sigmoid(z))
+              const BceRow b = bce_row(h, gr < dl.n_expert ? 1.f : 0.f, dl.scale);
+              dy = b.dl;
+#pragma unroll
+              for (int k = 0; k < 6; ++k) st[k] += b.st[k];
             }
           } else {
             dy = (gr < B && col < dout) ? dY[(size_t)gr * dout + col] : 0.f;

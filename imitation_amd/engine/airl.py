@@ -185,7 +185,7 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         z = lambda *sh, dt=th.float32: th.zeros(*sh, device=dev, dtype=dt)  # noqa: E731
         rows = 2 * mb
         self._disc_ws = dict(Xb=z(rows * din), S=z(rows * D), S2=z(rows * D), Act=z(rows * (1 if self.discrete else self.A)),
-                             Done=z(rows), partials=z(gblk * 4 * ncol), sums=z(2 * ncol, dt=th.float64), nrm=z(4 * 256),
+                             Done=z(rows), partials=z(self._C.airl_partials_floats(mb, ncol)), sums=z(2 * ncol, dt=th.float64), nrm=z(4 * 256),
                              slab=z((B // mb) * fblk * n), stats_slab=z((B // mb) * fblk * 8), grads=z(n))
         self._disc_stats = z(max(1, self.n_disc_updates_per_round), 8)
         g = self._disc_opt.param_groups[0]

@@ -326,7 +326,7 @@ class DeviceEngineMixin(DeviceGeneratorCore):
         assert n_params == n, (n_params, n)
         n_mb = B // mb
         z = lambda *sh, dt=th.float32: th.zeros(*sh, device=dev, dtype=dt)  # noqa: E731
-        self._disc_ws = dict(X=z(2 * mb, dims[0]), partials=z(gblk * 4 * dims[0]), slab=z(n_mb * fblk * n),
+        self._disc_ws = dict(X=z(2 * mb, dims[0]), partials=z(self._C.disc_partials_floats(mb, dims[0])), slab=z(n_mb * fblk * n),
                              stats_slab=z(n_mb * fblk * 8), grads=z(n), sums=z(2 * dims[0], dt=th.float64))
         self._disc_stats = z(max(1, self.n_disc_updates_per_round), 8)
         g = self._disc_opt.param_groups[0]

@@ -33,7 +33,6 @@ LR, BETA1, BETA2, ADAM_EPS = 1e-3, 0.9, 0.999, 1e-8
 EPS_B, EPS_P, EPS_Q = 1e-5, 1e-5, 1e-5
 GAMMA = 0.97
 ADAM_STEPS_TAKEN = 2  # the update under test is optimizer step 3
-MOMENT_SUMS = 4       # per gather block and column: S1, S2 under two shifts (airl_gather_kernel)
 # Placement of the hidden ReLU pre-activations of the reward nets and of the logit relative to 0
 # (make_case). The logit is r + gamma (1 - d) Phi(s') - Phi(s) - log pi: r and Phi get a small
 # spread, Phi a non-zero mean (so the (1 - d) factor and both signs show), and the base net's
@@ -533,7 +532,7 @@ class DevCase:
         nan = lambda *sh: th.full(sh, float("nan"), device=dev)  # noqa: E731
         ncol, npar = c.din + 2 * D, c.n_params
         self.ws = dict(Xb=nan(n * c.din), S=nan(n * D), S2=nan(n * D), Act=nan(n * (1 if c.discrete else c.A)), Done=nan(n),
-                       partials=nan(gblk * MOMENT_SUMS * ncol - partials_short), nrm=nan(4 * 256),
+                       partials=nan(C.airl_partials_floats(c.mb, ncol) - partials_short), nrm=nan(4 * 256),
                        slab=nan(c.n_mb * fblk * npar - slab_short), stats_slab=nan(c.n_mb * fblk * 8), grads=nan(npar),
                        sums=th.zeros(2 * ncol, device=dev, dtype=th.float64))
         src = {}

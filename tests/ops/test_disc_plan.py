@@ -384,7 +384,7 @@ class DevCase:
         # the trainer only takes a policy norm next to a reward net that sees the state
         self.pol = norm(c.pol) if L["use_state"] else None
         nan = lambda *sh: th.full(sh, float("nan"), device=dev)  # noqa: E731
-        self.ws = dict(X=nan(2 * c.mb, dims[0]), partials=nan(gblk * 4 * dims[0] - partials_short),
+        self.ws = dict(X=nan(2 * c.mb, dims[0]), partials=nan(C.disc_partials_floats(c.mb, dims[0]) - partials_short),
                        slab=nan(c.n_mb * fblk * n - slab_short), stats_slab=nan(c.n_mb * fblk * 8), grads=nan(n),
                        sums=th.zeros(2 * dims[0], device=dev, dtype=th.float64))
         src = {}
@@ -696,7 +696,7 @@ def test_input_wider_than_128_is_refused():
                 rew_count=z((), dt=th.int32), rew_eps=REW_EPS, obs_dim=D, act_width=A, use_state=1, use_action=1,
                 use_next_state=1, use_done=0, act_discrete=0, pol_mean=z(D), pol_var=z(D) + 1, pol_count=z((), dt=th.int32),
                 params=flat, exp_avg=z(flat.numel()), exp_avg_sq=z(flat.numel()), beta1=BETA1, beta2=BETA2, eps=ADAM_EPS,
-                weight_decay=0.0, X=X, partials=z(4 * din), slab=z(4 * flat.numel()), stats_slab=z(4 * 8),
+                weight_decay=0.0, X=X, partials=z(C.disc_partials_floats(4, din)), slab=z(4 * flat.numel()), stats_slab=z(4 * 8),
                 grads=z(flat.numel()), sums=z(2 * din, dt=th.float64), **src)
     idx = th.zeros(4, dtype=th.int64, device=dev)
     with pytest.raises(RuntimeError):
