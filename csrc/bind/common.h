@@ -48,3 +48,4 @@ void register_conv(py::module& m);
 void register_comm(py::module& m);
 void register_pref(py::module& m);
 void register_dqn(py::module& m);
+void register_bc_mlp(py::module& m);

@@ -17,6 +17,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_comm(m);
   register_pref(m);
   register_dqn(m);
+  register_bc_mlp(m);
   register_io(m);
   register_events(m);
 }

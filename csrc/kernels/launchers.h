@@ -353,6 +353,37 @@ struct DqnTdArgs {
 // hipErrorInvalidValue (nothing launched) outside D, H1, H2, A in 1..64 and n_a + n_e in 1..256
 hipError_t dqn_td_step(const DqnTdArgs& a, hipStream_t s);
 
+// ---- bc_mlp.hip: G behavioural-cloning minibatch steps of a two-hidden-layer MLP policy (gather,
+// forward, loss + the seven BC metrics, backward, L2, Adam over the whole bucket) in one
+// single-workgroup launch
+constexpr int kBcMlpMaxDim = 64;           // obs dim, both hidden widths, actions
+constexpr int kBcMlpMaxBatch = 256;        // rows per minibatch
+constexpr int kBcMlpMaxBucket = 64 * 1024; // elements of the flat bucket
+struct BcMlpArgs {
+  const float* obs_src;     // [rows, D]
+  const int64_t* acts_cat;  // [rows] (categorical head) or null
+  const float* acts_gauss;  // [rows, A] (Gaussian head) or null
+  int64_t rows;
+  const int64_t* ids;  // flat row ids [G, B]
+  int G, B;
+  int D, H1, H2, A;  // policy trunk D -> H1 -> H2 and action_net H2 -> A
+  int tanh_act;      // trunk activation: Tanh (1) or ReLU (0)
+  int off[6];        // offsets of the trunk's W1, b1, W2, b2 and action_net's W3, b3 in the bucket
+  int off_log_std;   // offset of log_std [A] (Gaussian head)
+  // the FusedAdam bucket of n floats (plain Adam: the L2 term is in the gradient): the kernel updates
+  // params and the moments of all n elements and advances *step by G; keep_grad: the last step's
+  // gradient is left in grads (otherwise grads is not touched)
+  float *params, *grads, *exp_avg, *exp_avg_sq, *step;
+  int64_t n;
+  int keep_grad;
+  float lr, beta1, beta2, eps;
+  float ent_weight, l2_weight;
+  float ent_weight_lo, l2_weight_lo;  // the weights are doubles on the host: w - (float)w, for the logged ent_loss / l2_loss
+  float* metrics;  // [G, 7]: neglogp, entropy, ent_loss, prob_true_act, l2_norm, l2_loss, loss
+};
+// hipErrorInvalidValue (nothing launched) outside D, H1, H2, A in 1..64, B in 1..256, n in 1..64K, G >= 1
+hipError_t bc_mlp_steps(const BcMlpArgs& a, hipStream_t s);
+
 // ---- dqn_collect.hip: K steps of epsilon-greedy acting, env physics and replay-ring writes for N
 // native vector envs in one launch (one wave per env)
 constexpr int kDqnCollectMaxSteps = 16;

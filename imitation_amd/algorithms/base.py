@@ -147,11 +147,18 @@ class TransitionsBatchLoader:
             return arr[idx]
         return np.asarray(arr)[idx]
 
-    def __iter__(self) -> Iterator[types.TransitionMapping]:
+    def epoch_order(self) -> np.ndarray:
+        """The row ids of the next epoch's batches, batch after batch (one permutation drawn from
+        the loader's generator when shuffling; cut to whole batches with ``drop_last``). What
+        ``__iter__`` slices; the device BC engine uploads it instead of iterating."""
         n = len(self.dataset)
         order = self._rng.permutation(n) if self.shuffle else np.arange(n)
         stop = n - (n % self.batch_size) if self.drop_last else n
-        for s in range(0, stop, self.batch_size):
+        return order[:stop]
+
+    def __iter__(self) -> Iterator[types.TransitionMapping]:
+        order = self.epoch_order()
+        for s in range(0, len(order), self.batch_size):
             idx = order[s : s + self.batch_size]
             batch = {}
             for k, v in self._fields.items():

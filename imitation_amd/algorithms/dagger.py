@@ -439,7 +439,8 @@ class SimpleDAggerTrainer(DAggerTrainer):
     and ``rollout_round_min_episodes`` episodes PER RANK (weak scaling; the expert acts
     deterministically), then aggregates and trains. ``total_timesteps`` counts the env
     steps of all ranks. Native image envs on a GPU collect with the device collector
-    (``device_collector='auto'``)."""
+    (``device_collector='auto'``; under a ``BC(engine="device")`` trainer ``'auto'`` keeps the
+    host collector, whose demonstration arrays that engine trains from)."""
 
     def __init__(self, *, venv, scratch_dir: types.AnyPath, expert_policy, rng: np.random.Generator,
                  expert_trajs: Optional[Sequence[types.Trajectory]] = None, device_collector: Union[str, bool] = "auto",
@@ -453,6 +454,10 @@ class SimpleDAggerTrainer(DAggerTrainer):
             self._store.write(traj, k, self.round_num, self.rng, prefix="initial_data")
         self._device_collector = None
         self._writer = None
+        if device_collector == "auto" and getattr(self.bc_trainer, "engine_kind", "host") == "device":
+            # BC's device engine trains from host demonstration arrays (device demo aggregates are
+            # the graph-epoch path's): 'auto' then keeps the host collector
+            device_collector = False
         if device_collector:
             from imitation_amd.engine import dagger as dagger_engine
 

@@ -26,16 +26,17 @@ def config():
     optimizer_kwargs = dict(lr=4e-4)
     train_kwargs = dict(n_epochs=None, n_batches=None, log_interval=500)
     agent_path = None  # serialized policy to start from
+    engine = "host"  # "device": fused MLP minibatch steps, whole runs per launch; "auto": when eligible
     locals()
 
 
 @bc_ingredient.capture
 def make_bc(venv, expert_trajs: Sequence[types.Trajectory], custom_logger, batch_size: int, l2_weight: float,
-            optimizer_cls, optimizer_kwargs, _rnd) -> bc.BC:
+            optimizer_cls, optimizer_kwargs, engine: str, _rnd) -> bc.BC:
     return bc.BC(observation_space=venv.observation_space, action_space=venv.action_space,
                  policy=make_or_load_policy(venv), demonstrations=expert_trajs, custom_logger=custom_logger, rng=_rnd,
                  batch_size=batch_size, l2_weight=l2_weight, optimizer_cls=optimizer_cls,
-                 optimizer_kwargs=optimizer_kwargs)
+                 optimizer_kwargs=optimizer_kwargs, engine=engine)
 
 
 @bc_ingredient.capture

@@ -52,7 +52,7 @@ def bc(bc: Dict[str, Any], _run, _rnd: np.random.Generator) -> Mapping[str, Mapp
             trainer.train(**kwargs)
         util.save_policy(trainer.policy, policy_path=osp.join(log_dir, "final.th"))
         imit_stats = policy_evaluation.eval_policy(trainer.policy, venv)
-    return _collect_stats(imit_stats, expert_trajs)
+    return dict(_collect_stats(imit_stats, expert_trajs), engine=trainer.engine_kind)
 
 
 @train_imitation_ex.command
@@ -118,6 +118,7 @@ def dagger(bc: Dict[str, Any], dagger: Mapping[str, Any], _run, _rnd: np.random.
         print(f"Model saved to {dagger_trainer.save_trainer()}")
         imit_stats = policy_evaluation.eval_policy(trainer.policy, venv)
     out = _collect_stats(imit_stats, dagger_trainer._all_demos)
+    out["engine"] = trainer.engine_kind
     if resume_meta is not None:
         out["resumed_round"] = int(resume_meta["step"])
     return out
@@ -141,7 +142,7 @@ def sqil(sqil: Mapping[str, Any], policy: Mapping[str, Any], rl: Mapping[str, An
             trainer.train(total_timesteps=int(sqil["total_timesteps"]), **train_kwargs)
         util.save_policy(trainer.policy, policy_path=osp.join(log_dir, "final.th"))
         imit_stats = policy_evaluation.eval_policy(trainer.policy, venv)
-    return _collect_stats(imit_stats, expert_trajs)
+    return dict(_collect_stats(imit_stats, expert_trajs), engine=trainer.engine_kind)
 
 
 def main_console(argv=None):
