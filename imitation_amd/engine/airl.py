@@ -29,22 +29,19 @@ cooperating-workgroup register-chained kernel.
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch as th
-
-from imitation_amd.utils.streams import shared_stream
-from imitation_amd.utils import profiling
 from numpy import prod as np_prod
 
-from imitation_amd.algorithms.adversarial import common
 from imitation_amd.algorithms.adversarial.airl import AIRL
-from imitation_amd.engine.gail import DeviceEngineMixin
-from imitation_amd.engine.generator import (OutputNormMixin, _FlatParams, _mlp_layers, _policy_nets, _split,
-                                            rollout_reward_mlp_ok, supports_generator)
+from imitation_amd.engine.adversarial import DeviceEngineMixin
+from imitation_amd.engine.generator import (OutputNormMixin, _mlp_layers, _policy_nets, _split, rollout_reward_mlp_ok,
+                                            supports_generator)
 from imitation_amd.parallel import dist as pdist
 from imitation_amd.rewards import reward_nets
 from imitation_amd.util import networks
+from imitation_amd.utils import profiling
 
 
 def supports(venv, gen_algo, reward_net) -> Tuple[bool, str]:
@@ -79,9 +76,7 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
 
     _host_cls_name = "algorithms.adversarial.airl.AIRL"
 
-    @staticmethod
-    def _supports(venv, gen_algo, reward_net):
-        return supports(venv, gen_algo, reward_net)
+    _supports = staticmethod(supports)
 
     def _reward_spec(self) -> Dict[str, Any]:
         _, shaped = _split(self._reward_net)
@@ -94,21 +89,17 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
                     use_done=int(base.use_done))
 
     # ------------------------------------------------------------------ fused discriminator (airl_disc.hip)
+    #: log pi needs the post-PPO policy: the updates follow PPO on the main stream, but the round is
+    #: pipelined like GAIL's (_overlapped_round: PPO stats copied async, the updates and the next
+    #: rollout enqueued before the host reads anything); IMITATION_AMD_DISC_OVERLAP=0: serial
+    _disc_on_main = True
+
     def _fused_disc_check(self) -> Tuple[bool, str]:
         if os.environ.get("IMITATION_AMD_AIRL_FUSED", "1") == "0":
             return False, "disabled (IMITATION_AMD_AIRL_FUSED=0)"
-        if type(self).logits_expert_is_high is not AIRL.logits_expert_is_high:
-            return False, "custom discriminator logits"
-        opt = self._disc_opt
-        if type(opt) is not th.optim.Adam or len(opt.param_groups) != 1:
-            return False, "discriminator optimizer is not a single-group torch.optim.Adam"
-        g = opt.param_groups[0]
-        if any(g.get(k) for k in ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")):
-            return False, "Adam variant not fused"
-        if self._init_tensorboard:
-            return False, "tensorboard summaries need per-step logits"
-        if not isinstance(self._endless_expert_iterator, common._DeviceDemoSampler):
-            return False, "demonstrations are not a flat device transitions set"
+        ok, why = self._common_disc_check(AIRL)
+        if not ok:
+            return ok, why
         _, shaped = _split(self._reward_net)
         try:
             bnorm, blins, _, bout = _mlp_layers(shaped.base.mlp)
@@ -125,10 +116,9 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
             return False, "MLP deeper than 4 layers"
         widths = [l.out_features for l in blins + plins + qlins] + [blins[0].in_features, plins[0].in_features,
                                                                     qlins[0].in_features]
-        if max(widths) > 64 or (self.A if not self.discrete else self.A) > 16:
+        if max(widths) > 64 or self.A > 16:
             return False, "MLP wider than 64"
-        mlp_params = {id(p) for l in blins + plins for p in (l.weight, l.bias)}
-        if {id(p) for p in self._reward_net.parameters()} != mlp_params:
+        if not self._reward_params_are(blins + plins):
             return False, "reward net has parameters outside its MLPs"
         base = shaped.base
         din = (base.use_state + base.use_next_state) * self.D + base.use_action * self.A + base.use_done
@@ -141,20 +131,7 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
             return False, "MLP images over the fused kernel's LDS limit"
         return True, ""
 
-    def _setup_fused_disc(self) -> None:
-        ok, why = self._fused_disc_check()
-        self._fused_disc = ok
-        self._fused_disc_why = why
-        # log pi needs the post-PPO policy: the updates follow PPO on the main stream, but the round
-        # is pipelined like GAIL's (_overlapped_round: PPO stats copied async, the updates and the
-        # next rollout enqueued before the host reads anything); IMITATION_AMD_DISC_OVERLAP=0: serial
-        self._overlap_disc = os.environ.get("IMITATION_AMD_DISC_OVERLAP", "1") != "0"
-        self._disc_on_main = True
-        self._side_stream = shared_stream(self._dev, "engine_side") if self._overlap_disc else None  # staging copies
-        self._pol_defer_buf = None
-        self._disc_split = False
-        if not ok:
-            return
+    def _setup_disc_plan(self) -> None:
         dev = self._dev
         _, shaped = _split(self._reward_net)
         base = shaped.base
@@ -162,20 +139,8 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         pnorm, plins, ph, _ = _mlp_layers(shaped.potential._potential_net)
         qnorm, qlins, _, qh = _policy_nets(self.gen_algo.policy)
         self._bnorm, self._pnorm = bnorm, pnorm
-        plist = []
-        for l in blins + plins:
-            plist += [l.weight, l.bias]
-        self._rflat = _FlatParams(plist)
+        ed = self._setup_disc_params(blins + plins)
         n = self._rflat.n
-        self._r_m = th.zeros(n, device=dev)
-        self._r_v = th.zeros(n, device=dev)
-        self._adopt_disc_opt_state()
-        ed = self._endless_expert_iterator.data
-        ed["obs"] = ed["obs"].float().contiguous()
-        ed["next_obs"] = ed["next_obs"].float().contiguous()
-        ed["acts"] = (ed["acts"].long() if self.discrete else ed["acts"].float()).reshape(ed["acts"].shape[0], -1)
-        ed["acts"] = ed["acts"].reshape(-1).contiguous() if self.discrete else ed["acts"].contiguous()
-        ed["dones"] = ed["dones"].bool().contiguous()
         gd = self._gen_dev._arrays
         B, mb = self.demo_batch_size, self.demo_minibatch_size
         gblk, fblk = self._C.airl_plan_sizes(mb)
@@ -187,7 +152,6 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         self._disc_ws = dict(Xb=z(rows * din), S=z(rows * D), S2=z(rows * D), Act=z(rows * (1 if self.discrete else self.A)),
                              Done=z(rows), partials=z(self._C.airl_partials_floats(mb, ncol)), sums=z(2 * ncol, dt=th.float64), nrm=z(4 * 256),
                              slab=z((B // mb) * fblk * n), stats_slab=z((B // mb) * fblk * 8), grads=z(n))
-        self._disc_stats = z(max(1, self.n_disc_updates_per_round), 8)
         g = self._disc_opt.param_groups[0]
         pol = self.gen_algo.policy
 
@@ -210,16 +174,30 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
                  beta2=float(g["betas"][1]), eps=float(g["eps"]), weight_decay=float(g.get("weight_decay", 0.0)),
                  **norm_args("b", bnorm), **norm_args("p", pnorm), **norm_args("q", qnorm), **self._disc_ws)
         self._disc_plan = self._C.AirlDiscPlan(d)
-        self._disc_stats_host = th.zeros(max(1, self.n_disc_updates_per_round), 8, pin_memory=True)
         # split rounds (single rank): the updates' gathers + norm merges are staged on the main
         # stream right after PPO, then the next rollout's step chain runs concurrently with the
-        # fwd/bwd + Adam applies on the side stream (see _overlapped_round)
+        # fwd/bwd + Adam applies on the side stream (see _split_round)
         # (data parallel too: the staging's normaliser all-reduces run on the main stream, the
         # applies' gradient all-reduces on the side stream, where nothing else uses the
         # communicator while they run -- the next step chain has no collectives)
         self._disc_split = (self._overlap_disc and os.environ.get("IMITATION_AMD_AIRL_SPLIT", "1") != "0")
         if self._disc_split:
             self._disc_plan.reserve(max(1, self.n_disc_updates_per_round))
+        self._q_deferred, self._q_defer_rows = False, 0  # _stage_disc_updates
+        self._early_staged_rounds = 0  # _split_round
+
+    def _disc_merges(self) -> Tuple[bool, bool, bool]:
+        """Which of the base, potential and policy RunningNorms merge an update's batch."""
+        return (self._bnorm is not None and self._bnorm.training, self._pnorm is not None and self._pnorm.training,
+                self.pol_norm is not None and self.pol_norm.training)
+
+    @profiling.traced("disc/update")
+    def _fused_disc_update(self, slot: int, defer_pol: bool = False, e_idx: Optional[th.Tensor] = None,
+                           g_idx: Optional[th.Tensor] = None, apply: bool = True) -> None:
+        """One discriminator optimizer step (== AdversarialTrainer.train_disc with AIRL's logits)
+        on the fused kernels, with no host sync. ``e_idx`` / ``g_idx``: explicit expert / replay
+        rows (tests); ``apply=False`` stops after the gradient reduction (``_disc_ws["grads"]``)."""
+        self._run_disc_update(slot, self._disc_merges(), e_idx, g_idx, apply)
 
     @profiling.traced("disc/stage")
     def _stage_disc_updates(self, n: int, defer_q: bool = False) -> List[Tuple[float, float]]:
@@ -232,54 +210,42 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
         PPO), so the staging can run on the side stream during the PPO update (under DP its
         normaliser all-reduces then run there too); ``self._q_deferred`` says whether there is
         anything to merge."""
-        if self._gen_dev.size() == 0:
-            raise RuntimeError("No generator samples for training. Call `train_gen()` first.")
         # (grows only here: the previous round's applies were waited for on the host)
         self._disc_plan.reserve(max(1, n))
-        opt = self._disc_opt
         self._adopt_disc_opt_state()
-        g = opt.param_groups[0]
-        beta1, beta2 = g["betas"]
-        t0 = float(opt.state[self._rflat.params[0]]["step"])
-        B = self.demo_batch_size
-        merge_b = self._bnorm is not None and self._bnorm.training
-        merge_p = self._pnorm is not None and self._pnorm.training
-        merge_q = self.pol_norm is not None and self.pol_norm.training
+        merges = self._disc_merges()
         scal = []
         world = pdist.world_size()
-        defer_q = defer_q and merge_q
+        defer_q = defer_q and merges[2]
         self._q_deferred = defer_q
         synced = world > 1 and pdist.norm_sync_active()
-        self._q_defer_rows = 2 * self.demo_minibatch_size * (world if synced else 1)
+        mb = self.demo_minibatch_size
+        self._q_defer_rows = 2 * mb * (world if synced else 1)
         cur = th.cuda.current_stream(self._dev)
         for i in range(n):
-            e_idx = self._endless_expert_iterator.next_indices()
+            e_idx, g_idx = self._draw_disc_indices()
             # the epoch permutation may come from another stream's pool: keep its block alive
             # for this stream's reads
             e_idx.record_stream(cur)
-            g_idx = th.randint(0, self._gen_dev.size(), (B,), device=self._dev)
-            if world == 1 or not pdist.norm_sync_active():
-                self._disc_plan.stage(i, e_idx, g_idx, merge_b, merge_p, merge_q, defer_q)
+            if not synced:
+                self._disc_plan.stage(i, e_idx, g_idx, *merges, defer_q)
             else:  # the DP update's order: gather, moments, all-reduce, merges -- per minibatch
-                mb = self.demo_minibatch_size
-                for k in range(B // mb):
-                    self._disc_plan.stage_part(i, k, e_idx, g_idx, 1, 0, merge_b, merge_p, merge_q)
+                for k in range(self.demo_batch_size // mb):
+                    self._disc_plan.stage_part(i, k, e_idx, g_idx, 1, 0, *merges)
                     pdist.allreduce_sum_(self._disc_ws["sums"])
-                    self._disc_plan.stage_part(i, k, e_idx, g_idx, 2, 2 * mb * world, merge_b, merge_p, merge_q, defer_q)
-            t = t0 + i + 1.0
-            scal.append((float(g["lr"]) / (1.0 - beta1**t), (1.0 - beta2**t) ** 0.5))
+                    self._disc_plan.stage_part(i, k, e_idx, g_idx, 2, 2 * mb * world, *merges, defer_q)
+            scal.append(self._adam_scalars(i + 1))
         return scal
 
     def _merge_deferred_q(self, n: int) -> None:
         """The policy-norm merges ``_stage_disc_updates(n, defer_q=True)`` left (update order)."""
-        if getattr(self, "_q_deferred", False):
+        if self._q_deferred:
             self._disc_plan.q_merge(n, self._q_defer_rows)
             self._q_deferred = False
 
     @profiling.traced("disc/apply")
     def _apply_disc_updates(self, scal: List[Tuple[float, float]], steps: List[int]) -> None:
         """The fwd/bwd passes and Adam steps of the staged updates (``AirlDiscPlan.apply``)."""
-        opt = self._disc_opt
         world = pdist.world_size()
         for i, (step_size, bc2_sqrt) in enumerate(scal):
             if world == 1:
@@ -288,55 +254,72 @@ class DeviceAIRL(OutputNormMixin, DeviceEngineMixin, AIRL):
                 self._disc_plan.apply_grads(i, self._disc_stats[i])
                 pdist.allreduce_grads_flat(self._disc_ws["grads"])
                 self._disc_plan.adam(0, 1, step_size, bc2_sqrt, None)
-            for p in self._rflat.params:
-                opt.state[p]["step"] += 1
-            self._disc_step += 1
+            self._bump_disc_step()
             steps.append(self._disc_step)
 
-    @profiling.traced("disc/update")
-    def _fused_disc_update(self, slot: int, defer_pol: bool = False, e_idx: th.Tensor = None, g_idx: th.Tensor = None,
-                           apply: bool = True) -> None:
-        """One discriminator optimizer step (== AdversarialTrainer.train_disc with AIRL's logits)
-        on the fused kernels, with no host sync. ``e_idx`` / ``g_idx``: explicit expert / replay
-        rows (tests); ``apply=False`` stops after the gradient reduction (``_disc_ws["grads"]``)."""
-        if self._gen_dev.size() == 0:
-            raise RuntimeError("No generator samples for training. Call `train_gen()` first.")
-        opt = self._disc_opt
-        self._adopt_disc_opt_state()
-        g = opt.param_groups[0]
-        t = float(opt.state[self._rflat.params[0]]["step"]) + 1.0
-        beta1, beta2 = g["betas"]
-        step_size = float(g["lr"]) / (1.0 - beta1**t)
-        bc2_sqrt = (1.0 - beta2**t) ** 0.5
-        B, mb = self.demo_batch_size, self.demo_minibatch_size
-        if e_idx is None:
-            e_idx = self._endless_expert_iterator.next_indices()
-        if g_idx is None:
-            g_idx = th.randint(0, self._gen_dev.size(), (B,), device=self._dev)
-        merge_b = self._bnorm is not None and self._bnorm.training
-        merge_p = self._pnorm is not None and self._pnorm.training
-        merge_q = self.pol_norm is not None and self.pol_norm.training
-        plan = self._disc_plan
-        stats_out = self._disc_stats[slot]
-        if pdist.world_size() == 1 and apply:
-            plan.update(e_idx, g_idx, step_size, bc2_sqrt, merge_b, merge_p, merge_q, stats_out)
+    # ------------------------------------------------------------------ split rounds
+    def _after_ppo(self, n: int, ready: th.cuda.Event, launch_next: bool, defer_pol: bool):
+        if self._disc_split and n > 0:
+            return self._split_round(n, launch_next)
+        return super()._after_ppo(n, ready, launch_next, defer_pol)
+
+    def _stage_during_ppo(self) -> bool:
+        """Split-round staging on the side stream, concurrent with PPO. Under data parallelism
+        only with the replicated PPO update, which issues no collective: the staging's normaliser
+        all-reduces are then the only users of the communicator while they run.
+        IMITATION_AMD_AIRL_EARLY_STAGE=0: stage behind PPO on the main stream."""
+        return ((pdist.world_size() == 1 or self._dp_replicated) and self._host_staged
+                and os.environ.get("IMITATION_AMD_AIRL_EARLY_STAGE", "1") != "0")
+
+    def _split_round(self, n: int, launch_next: bool) -> Tuple[List[int], Optional[th.cuda.Event]]:
+        """Rest of a split round after PPO (instead of the mixin's ``_after_ppo``). The updates'
+        gathers + norm merges are the only part of them that the next rollout's step chain depends
+        on (through the policy RunningNorm): stage them on the main stream, apply the updates
+        (fwd/bwd + Adam) on the side stream while that step chain runs, then the rollout's reward
+        pass behind the applies."""
+        main = th.cuda.current_stream(self._dev)
+        side = self._side_stream
+        ppo_done = self._ppo_done
+        steps: List[int] = []
+        if self._stage_during_ppo():
+            # replay store, gathers and base / potential merges on the side stream while PPO
+            # runs (none of it touches the policy norm or the policy); then the policy-norm
+            # merges, one launch, behind PPO on the main stream. The side stream is already
+            # ordered after the rollout (_stage_rollout_to_host).
+            with th.cuda.stream(side):
+                self._store_generator_samples()
+                with networks.training(self.reward_train):
+                    scal = self._stage_disc_updates(n, defer_q=True)
+                side_staged = self._dev_event(side)
+            self._wait_ev(main, side_staged)
+            self._merge_deferred_q(n)
+            self._early_staged_rounds += 1
         else:
-            world = pdist.world_size()
-            for k in range(B // mb):
-                plan.gather(k, e_idx, g_idx)
-                if pdist.norm_sync_active():
-                    plan.norm(1, 0, merge_b, merge_p, merge_q)
-                    pdist.allreduce_sum_(self._disc_ws["sums"])
-                    plan.norm(2, 2 * mb * world, merge_b, merge_p, merge_q)
-                else:
-                    plan.norm(0, 0, merge_b, merge_p, merge_q)
-                plan.fwd_bwd(k)
-            plan.adam(1, 0, 0.0, 1.0, stats_out)
-            if world > 1:
-                pdist.allreduce_grads_flat(self._disc_ws["grads"])
-            if not apply:
-                return
-            plan.adam(0, 1, step_size, bc2_sqrt, None)
-        for p in self._rflat.params:
-            opt.state[p]["step"] += 1
-        self._disc_step += 1
+            self._store_generator_samples()
+            with networks.training(self.reward_train):
+                scal = self._stage_disc_updates(n)
+        staged = self._dev_event(main)
+        # the next step chain is enqueued before the applies (host order only: it depends on
+        # the staging, not on the applies), so a slow host never delays its start
+        if launch_next:
+            self._launch_chain()
+        self._wait_ev(side, staged)
+        with th.cuda.stream(side):
+            self._apply_disc_updates(scal, steps)
+            disc_dev = self._dev_event(side)
+            self._disc_stats_host[:n].copy_(self._disc_stats[:n], non_blocking=True)
+            disc_done = th.cuda.Event()
+            disc_done.record(side)
+        self._global_step += 1
+        nxt = None
+        self._wait_ev(main, disc_dev)
+        if launch_next:
+            reward = not self.debug_use_ground_truth
+            self._launch_post(reward)
+            if reward:
+                self._post_rollout_rewards()
+            nxt = self._stage_rollout_to_host()
+        ppo_done.synchronize()
+        self._log_gen()
+        disc_done.synchronize()
+        return steps, nxt

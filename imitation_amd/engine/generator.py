@@ -1,7 +1,7 @@
 """The device PPO generator every device engine shares (:class:`DeviceGeneratorCore`; the table
 in :mod:`imitation_amd.engine.gail` maps its kernels to the reference's host loop) and the
 device replay of ``NormalizedRewardNet`` output normalisation (:class:`OutputNormMixin`).
-The trainers' engines (:mod:`.gail`, :mod:`.airl`, :mod:`.preference`, :mod:`.rl`) build on
+The trainers' engines (:mod:`.adversarial` with :mod:`.gail` and :mod:`.airl`, :mod:`.preference`, :mod:`.rl`) build on
 this module; it imports none of them."""
 
 from __future__ import annotations
@@ -166,7 +166,7 @@ class _FlatParams:
 class DeviceGeneratorCore:
     """Device PPO generator: env state, flat policy parameters, the fused rollout kernel
     (policy + env + learned reward), GAE and the PPO update kernels, data-parallel plan.
-    Shared by the adversarial engines (:class:`imitation_amd.engine.gail.DeviceEngineMixin`), the
+    Shared by the adversarial engines (:class:`imitation_amd.engine.adversarial.DeviceEngineMixin`), the
     preference-comparison agent (:class:`imitation_amd.engine.preference.DeviceAgentTrainer`) and
     ``train_rl`` (:class:`imitation_amd.engine.rl.DevicePPO`).
     Subclasses set ``gen_algo``, ``_reward_net`` and ``debug_use_ground_truth`` and call
@@ -263,7 +263,7 @@ class DeviceGeneratorCore:
         self._ppo_log_host = self._ppo_std_host = self._log_stream = self._ppo_log_event = None  # _stage_ppo_logs
         self._ppo_done = self._last_ppo_info = self._last_clip_range = self._last_lr = None  # _ppo_update
         self._host_stage, self._host_staged = None, False  # _stage_rollout_to_host
-        self._side_stream = None  # (the adversarial engines' _setup_fused_disc)
+        self._side_stream = None  # (engine/adversarial.py _setup_fused_disc)
         self._fps_mark = (None, None)
 
     def _env_mirror(self, st: Mapping[str, np.ndarray], obs0) -> Dict[str, th.Tensor]:

@@ -701,7 +701,7 @@ def test_ppo_kernel_timeout_raises(batch, path):
 
 @gpu
 def test_airl_pipelined_rounds_are_bitwise_the_serial_order(monkeypatch):
-    """AIRL rounds pipelined on the main stream (engine/gail.py ``_overlapped_round`` with
+    """AIRL rounds pipelined on the main stream (engine/adversarial.py ``_overlapped_round`` with
     ``_disc_on_main``: PPO statistics copied asynchronously, the discriminator updates and the next
     rollout enqueued before the host reads anything) give bit-identical parameters, Adam moments
     and normalisers to the serial loop (IMITATION_AMD_DISC_OVERLAP=0) -- also as split rounds

@@ -1,4 +1,4 @@
-"""The vectorised replay order of a device round (engine/gail.py flatten_order) == the
+"""The vectorised replay order of a device round (engine/adversarial.py flatten_order) == the
 per-step loop of BufferingWrapper -> flatten -> FIFO store it replaces (CPU)."""
 
 import numpy as np

@@ -11,7 +11,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-_ADVERSARIAL = ("imitation_amd.engine.gail", "imitation_amd.engine.airl")
+_ADVERSARIAL = ("imitation_amd.engine.adversarial", "imitation_amd.engine.gail", "imitation_amd.engine.airl")
 
 CASES = {
     "imitation_amd.engine.generator": _ADVERSARIAL + ("imitation_amd.engine.preference",
