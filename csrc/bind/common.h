@@ -49,3 +49,4 @@ void register_comm(py::module& m);
 void register_pref(py::module& m);
 void register_dqn(py::module& m);
 void register_bc_mlp(py::module& m);
+void register_sac(py::module& m);

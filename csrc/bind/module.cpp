@@ -18,6 +18,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_pref(m);
   register_dqn(m);
   register_bc_mlp(m);
+  register_sac(m);
   register_io(m);
   register_events(m);
 }

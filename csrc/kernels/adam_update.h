@@ -1,6 +1,6 @@
 // The per-element Adam / AdamW update and its bias corrections, shared by every kernel that
-// steps a FusedAdam bucket (optim.hip's adam_flat, the in-launch steps of dqn_td.hip and
-// bc_mlp.hip): one body, so the kernels produce the same bits from the same state.
+// steps a FusedAdam bucket (optim.hip's adam_flat, the in-launch steps of dqn_td.hip, bc_mlp.hip
+// and sac_update.hip): one body, so the kernels produce the same bits from the same state.
 #pragma once
 #include <hip/hip_runtime.h>
 

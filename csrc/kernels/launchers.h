@@ -423,6 +423,45 @@ struct DqnCollectArgs {
 // not a discrete-action vector env of these D and A, and for a threshold above 2^24
 hipError_t dqn_collect(const DqnCollectArgs& a, hipStream_t s);
 
+// ---- sac_update.hip: every gradient step of one SAC.train call (gather, actor forwards, entropy
+// coefficient, target, critic update, actor update, Polyak) in one single-workgroup launch
+constexpr int kSacMaxDim = 64;     // obs dim, hidden widths, obs dim + action dim
+constexpr int kSacMaxBatch = 256;  // rows per gradient step
+struct SacSrc {  // a replay ring viewed as [rows] flat (step * n_envs + env) rows
+  const float *obs, *next_obs;  // [rows, D]
+  const float* action;          // [rows, A]
+  const float *reward, *done, *timeout;  // [rows]; effective done = done * (1 - timeout)
+  int64_t rows;
+};
+struct SacBucket {  // a FusedAdam bucket of n floats (plain Adam) and its hyper-parameters
+  float *params, *grads, *exp_avg, *exp_avg_sq, *step;
+  int64_t n;
+  float lr, beta1, beta2, eps;
+};
+struct SacUpdateArgs {
+  SacSrc src[2];  // the agent ring (first n_a rows of a batch) and SQIL's expert ring (last n_e; 0 for plain SAC)
+  const int64_t *ids_a, *ids_b;      // flat row ids [G, n_a], [G, n_e]
+  const float *eps_pi, *eps_next;    // the actor's noise on obs / next_obs, [G, n_a + n_e, A] each
+  int G, n_a, n_e;
+  int D, A;          // obs dim, action dim (D + A <= 64)
+  int aH1, aH2;      // actor trunk D -> aH1 -> aH2 (ReLU), heads mu / log_std: aH2 -> A
+  int cH1, cH2;      // each critic D + A -> cH1 -> cH2 -> 1 (ReLU)
+  int a_off[8];      // actor bucket: W1, b1, W2, b2, Wmu, bmu, Wls, bls
+  int c_off[2][6];   // critic and target buckets: W1, b1, W2, b2, W3, b3 of qf0 and qf1
+  // the kernel updates params and moments, advances *step by G and leaves the last step's gradient in grads
+  SacBucket actor, critic;
+  SacBucket ent;     // log_ent_coef (element 0); params == nullptr: the fixed coefficient ent_coef_fixed
+  float ent_coef_fixed;
+  float target_entropy;
+  float* target;     // the target critics' flat bucket (critic.n floats)
+  float gamma, tau, one_minus_tau;
+  int target_update_interval;  // Polyak after step g iff g % interval == 0
+  float *critic_loss, *actor_loss, *ent_coef, *ent_coef_loss;  // [G] each (ent_coef_loss: 0 with a fixed coefficient)
+};
+// hipErrorInvalidValue (nothing launched) outside D, aH1, aH2, cH1, cH2 in 1..64, A >= 1, D + A <= 64,
+// n_a + n_e in 1..256, G >= 1, for a null pointer and for an offset outside its bucket
+hipError_t sac_update_step(const SacUpdateArgs& a, hipStream_t s);
+
 // ---- rl.hip: GAE scan over [T, N]
 hipError_t gae_launch(const float* rew, const float* val, const float* starts, const float* last_val, const float* dones,
                       int T, int N, float gamma, float lam, float* adv, float* ret, hipStream_t s,

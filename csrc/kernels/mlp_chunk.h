@@ -1,4 +1,4 @@
-// fp32 row-chunk helpers of the one-workgroup training kernels (dqn_td.hip, bc_mlp.hip): a chunk
+// fp32 row-chunk helpers of the one-workgroup training kernels (dqn_td.hip, bc_mlp.hip, sac_update.hip): a chunk
 // of up to 64 rows has its activations in LDS as [kR][kS] images; `stage` puts one layer's weights
 // into LDS, `layer` is the chunk's GEMM with the bias, `wgrad` the owning thread's dW sums. fp32
 // FMAs in a fixed order: equal inputs give equal bits.
@@ -61,6 +61,36 @@ __device__ __forceinline__ void layer(int tid, const float* sIn, const float* sW
   for (int i = 0; i < 16; ++i) {
     float v = acc[i];
     if (RELU) v = fmaxf(v, 0.f);
+    if (MASK) v = sMask[(r0 + i) * kS + j] > 0.f ? v : 0.f;
+    sOut[(r0 + i) * kS + j] = j < nout ? v : 0.f;
+  }
+}
+
+// `layer` without the bias and the ReLU, on top of an earlier product: sOut[r][j] = sInit[r][j] +
+// sum_k sIn[r][k] * sW[k][j] (the backward of two heads on one trunk). sOut may be sInit or sMask:
+// a thread reads and writes its own elements only.
+template <bool MASK>
+__device__ __forceinline__ void layer_acc(int tid, const float* sIn, const float* sW, const float* sInit, int red, int nout, int nr,
+                                          const float* sMask, float* sOut) {
+  const int j = tid & 63, r0 = (tid >> 6) * 16;
+  if (r0 >= nr) return;  // (wave uniform)
+  float acc[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = sInit[(r0 + i) * kS + j];
+  for (int k = 0; k < red; k += 4) {
+    const float w0 = sW[k * kWS + j], w1 = sW[(k + 1) * kWS + j], w2 = sW[(k + 2) * kWS + j], w3 = sW[(k + 3) * kWS + j];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float4 x = *reinterpret_cast<const float4*>(sIn + (r0 + i) * kS + k);
+      acc[i] = __builtin_fmaf(x.x, w0, acc[i]);
+      acc[i] = __builtin_fmaf(x.y, w1, acc[i]);
+      acc[i] = __builtin_fmaf(x.z, w2, acc[i]);
+      acc[i] = __builtin_fmaf(x.w, w3, acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    float v = acc[i];
     if (MASK) v = sMask[(r0 + i) * kS + j] > 0.f ? v : 0.f;
     sOut[(r0 + i) * kS + j] = j < nout ? v : 0.f;
   }
